@@ -2,7 +2,16 @@
 """bench.py -- headline benchmark (BASELINE.json: "BPE merges/sec + pair-count
 GB/s vs HBM roofline").
 
-    python bench.py [--gpus N --steps K --warmup W] [--workload NAME] [--secondary a,b]
+    python bench.py [--gpus N --steps K --warmup W] [--workload NAME] [--dump-outputs DIR]
+    python bench.py --full [--secondary a,b] [...]
+
+A plain run sets up, warms up for W steps, times K steps without event records, writes the
+outputs of the last timed step if --dump-outputs is given, and prints its line: `value`
+(merges/s) and `ms_per_step` of the timed steps, nothing else measured or checked.  --full
+adds everything described below (the per-kernel breakdown and roofline, the parity and
+invariant checks, cpu_baseline, the secondary workloads; at N > 1 the sharded checks), as
+it always ran; there the timed steps carry the hipEvent records the roofline is read from.
+The encode and encode_long workloads always print their whole line.
 
 Workloads (one "step" = one complete train() from bytes already resident in HBM:
 widen to ids, initial get_stats, then vocab-256 x (arg-max with the reference's
@@ -16,19 +25,20 @@ tie-break, merge, pair-table update)):
   cfg2     BASELINE.json configs[1]: BasicTokenizer.train, 100 MB (seed 1), vocab 4096.
   encode   BASELINE.json configs[4] shape: batch encode of documents (own vocabulary).
 
-The headline workload is timed for --steps; the --secondary workloads (default
+The headline workload is timed for --steps; with --full the --secondary workloads (default
 basic1g,cfg2,regex1g_dedup,e2e_class,literal_path,encode,encode_long at N=1) run --secondary-steps each after it and are reported under
 "secondary".  N > 1: the chunk list of regex1g is sharded (contiguous chunk ranges,
 --bytes per GPU = cfg4 shape, weak scaling); `value` = what ALL ranks processed per second
 (N x the job's merges/s: a merge of the one sharded job is applied to every rank's shard --
 the bench contract's whole-job aggregate), `job_merges_per_s` = the rate of the ONE job.
 
-Prints ONE JSON line on rank 0.  `roofline` = the dominant kernel class timed with
+Prints ONE JSON line on rank 0.  With --full: `roofline` = the dominant kernel class timed with
 hipEvents on the library's own stream inside the timed steps; `cpu_baseline` = the CPU
 oracle (C restatement of the reference loop, one thread) on a bounded slice of the same
 input, on this host, plus minbpe's pure-Python loop (oracle/pyref.py, a pinned restatement) on a smaller slice.
-Parity with the oracle is CHECKED in the run against committed full-length digests
-(tests/golden/big_golden.json) and reported, never assumed.
+Parity with the oracle is CHECKED in a --full run against committed full-length digests
+(tests/golden/big_golden.json) and reported, never assumed; a plain run's outputs can be
+compared with another build's through --dump-outputs.
 """
 import argparse
 import hashlib
@@ -196,11 +206,11 @@ def make_input(wl, rank=0):
     return data, offs, time.perf_counter() - t0
 
 
-def run_train_workload(name, wl, eng, steps, warmup, barrier, reduce_max, mode, secondary=False):
-    """Upload once, warm up, one untimed step with events around every kernel class (the
-    breakdown), then `steps` timed steps with events around the merge pass only."""
+def run_train_workload(name, wl, eng, steps, warmup, barrier, reduce_max, mode, secondary=False, full=True):
+    """Upload once, warm up, then `steps` timed steps.  full: one untimed step with events around every kernel
+    class (the breakdown) before them, events around the merge pass only during them, and the parity, invariant
+    and roofline figures after them; otherwise the timed steps alone, without event records."""
     data, offs, prep_s = make_input(wl)
-    data_sha = hashlib.sha256(data).hexdigest()
     num_merges = wl["vocab"] - 256
     if mode >= 0:
         eng.set_option("mode", mode)
@@ -210,36 +220,42 @@ def run_train_workload(name, wl, eng, steps, warmup, barrier, reduce_max, mode, 
     step = lambda: eng.train(num_merges)
     for _ in range(warmup):
         step()
-    eng.set_option("profile", 2)  # (hipEvents around every kernel class; sampled like profile 1, see below)
-    eng.prof_reset()
-    step()
-    breakdown = eng.prof_read()
-    eng.set_option("profile", 1)
-    eng.prof_reset()
+    if full:
+        eng.set_option("profile", 2)  # (hipEvents around every kernel class; sampled like profile 1, see below)
+        eng.prof_reset()
+        step()
+        breakdown = eng.prof_read()
+        eng.set_option("profile", 1)
+        eng.prof_reset()
     barrier()
     t0 = time.perf_counter()
     for _ in range(steps):
         res = step()
     barrier()
     dt = reduce_max(time.perf_counter() - t0)
+    out = {
+        "workload": f"{wl['desc']}, {wl['bytes']} B synthetic UTF-8 (seed {wl['seed']}), vocab {wl['vocab']} "
+                    f"({num_merges} merges)" + (f", {len(offs)} chunks" if offs is not None else ""),
+        "steps": steps, "ms_per_step": round(dt / steps * 1e3, 3),
+        "merges_per_s": round(num_merges * steps / dt, 2),
+    }
+    if not full:
+        return out, data, offs, res
+    data_sha = hashlib.sha256(data).hexdigest()
     prof = eng.prof_read()
     eng.set_option("profile", 0)
     # the same step without the event records of the timed region (what they cost: an event drains the queue)
     t0 = time.perf_counter()
     step()
     plain_ms = (time.perf_counter() - t0) * 1e3
-    out = {
-        "workload": f"{wl['desc']}, {wl['bytes']} B synthetic UTF-8 (seed {wl['seed']}), vocab {wl['vocab']} "
-                    f"({num_merges} merges)" + (f", {len(offs)} chunks" if offs is not None else ""),
-        "steps": steps, "ms_per_step": round(dt / steps * 1e3, 3),
-        "merges_per_s": round(num_merges * steps / dt, 2),
+    out.update({
         "ms_per_step_without_event_records": round(plain_ms, 3),
         "host_prep_s": round(prep_s, 2), "upload_s": round(upload_s, 3),
         "pcie_inclusive_merges_per_s": round(num_merges / (dt / steps + upload_s), 2),
         "final_len": res["lens"][-1] if res["lens"] else len(data),
         "parity": parity_report(name, wl, data_sha, offs, res),
         "invariants": invariants(res, len(data)),
-    }
+    })
     # dominant kernel class by device time -> roofline (timed live in the timed region: hipEvents on the
     # library's stream around that class, every iteration up to 1024 and every 64th after, weighted)
     hot = max(("pair_count", "merge", "widen"), key=lambda k: breakdown[k]["ms"])
@@ -780,6 +796,19 @@ def parity_failures(obj, path=""):
     return bad
 
 
+def dump_outputs(d, res):
+    """What a caller of train() receives from the last timed step, as float64 arrays (ids and counts are exact
+    there): pairs (n, 2), counts (n,), lens (n,) -- the stream length after each merge."""
+    import numpy as np
+    os.makedirs(d, exist_ok=True)
+    n = len(res["pairs"])
+    for key, arr in (("pairs", np.asarray(res["pairs"], dtype=np.float64).reshape(n, 2)),
+                     ("counts", np.asarray(res["counts"], dtype=np.float64)),
+                     ("lens", np.asarray(res["lens"], dtype=np.float64))):
+        assert arr.nbytes <= 16 << 20
+        np.save(os.path.join(d, key + ".npy"), arr)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -798,7 +827,20 @@ def main():
     ap.add_argument("--cpu-iters", type=int, default=40, help="oracle iterations for cpu_baseline (0 = skip)")
     ap.add_argument("--cpu-bytes", type=int, default=100_000_000, help="slice of the input the oracle is timed on")
     ap.add_argument("--opt", action="append", default=[], help="engine option name=value (experiments)")
+    ap.add_argument("--full", action="store_true",
+                    help="also the figures beyond the headline: the per-kernel breakdown and roofline (hipEvents in the "
+                         "timed steps), parity with the committed oracle digests and the invariants, cpu_baseline and "
+                         "the secondary workloads; N > 1 adds the ranks' agreement and the single-GPU comparison")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step returned (train(): pairs, counts, lens) as DIR/<name>.npy, "
+                         "float64")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if not args.full and args.secondary not in (None, "none"):
+        ap.error("--secondary needs --full")
+    if args.dump_outputs and args.workload in ("encode", "encode_long"):
+        ap.error("--dump-outputs writes the outputs of train(): not of the encode workloads")
 
     import torch  # device sync + torch.distributed (RCCL) plumbing only
     import torch.distributed as dist
@@ -862,8 +904,26 @@ def main():
         if getattr(args, k) is not None:
             wl[k] = getattr(args, k)
 
-    if not sharded:
+    if not sharded and not args.full:
+        # the headline alone: set up, warm up, the timed steps (the figures beyond them: --full)
+        r, data, offs, res = run_train_workload(name, wl, eng, args.steps, args.warmup, barrier, reduce_max, args.mode,
+                                                full=False)
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, res)
+        line.update({
+            "value": r["merges_per_s"], "ms_per_step": r["ms_per_step"],
+            "config": {"workload": (f"{name}: {'Regex' if wl['chunked'] else 'Basic'}Tokenizer.train, "
+                                    f"{wl['bytes'] / 1e9:g} GB synth seed {wl['seed']}, vocab {wl['vocab']}")[:119],
+                       "workload_detail": r["workload"],
+                       "mode": "recount" if args.mode == 0 else ("delta" if args.mode == 1 else "default"),
+                       "parallelism": "single"},
+            "roofline": None, "cpu_baseline": None,
+        })
+        del data, offs, res
+    elif not sharded:
         r, data, offs, res = run_train_workload(name, wl, eng, args.steps, args.warmup, barrier, reduce_max, args.mode)
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, res)
         cpu = None
         if args.cpu_iters > 0:
             cpu = cpu_baseline(wl, data, offs, res, args.cpu_bytes, args.cpu_iters)
@@ -950,146 +1010,162 @@ def main():
             step = lambda: train_sharded(shard, comm, num_merges)
         for _ in range(args.warmup):
             step()
-        try:  # hipEvents around this rank's merge passes during the timed steps (as at N = 1)
-            eng.set_option("profile", 1)
-            eng.prof_reset()
-        except Exception:
-            pass
+        if args.full:
+            try:  # hipEvents around this rank's merge passes during the timed steps (as at N = 1)
+                eng.set_option("profile", 1)
+                eng.prof_reset()
+            except Exception:
+                pass
         barrier()
         t0 = time.perf_counter()
         for _ in range(args.steps):
             res = step()
         barrier()
         dt = reduce_max(time.perf_counter() - t0)
-        roofline = None
-        try:
-            mg = eng.prof_read()["merge"]
-            eng.set_option("profile", 0)
-            n0 = torch.tensor([len(data)], dtype=torch.int64, device="cuda")
-            dist.all_reduce(n0, op=dist.ReduceOp.SUM)
-            lens = [int(n0.item())] + [int(x) for x in res["lens"]]  # GLOBAL stream lengths
-            alg = sum(4 * (2 * lens[i] + lens[i + 1]) for i in range(len(lens) - 1)) * args.steps / world
-            if mg["ms"] > 0 and mg["launches"]:
-                ach = alg / (mg["ms"] * 1e-3) / 1e9
-                roofline = {
-                    "bound": "hbm", "kernel": "merge pass of rank 0 on its shard: k_merge_chain | k_merge_chain_dense | "
-                                             "k_merge_chain_dense1 (a chain step) | k_merge_ab_* + k_merge_aa (a general iteration)",
-                    "achieved": round(ach, 1), "peak": HBM_PEAK_GBPS, "unit": "GB/s",
-                    "frac": round(ach / HBM_PEAK_GBPS, 4), "traffic": None,
-                    "launches": mg["launches"], "avg_launch_ms": round(mg["ms"] / mg["launches"], 5),
-                    "alg_bytes_per_launch": int(alg // mg["launches"]),
-                    "achieved_kind": "algorithmic (SURVEY 8d bytes / hipEvent time)",
-                    "note": "per GPU: the job's algorithmic bytes (4(2N_i + N_{i+1}) on GLOBAL lengths) / world, over "
-                            "the hipEvent time of rank 0's merge passes",
-                }
-                # physical: counters cannot be read inside a run; a rank's merge passes work on a shard of the single-GPU
-                # headline's size with the same kernels, so the committed single-GPU PMC profile's bytes per merge give
-                # an ESTIMATE of this rank's traffic (labelled as such; the per-launch figure does not carry over:
-                # a sharded step's batch is capped lower)
-                pmc_file = os.path.join(ROOT, "profiles", f"{PROFILE_ROUND}_regex1g_pmc.json")
-                if os.path.exists(pmc_file) and wl["bytes"] == WORKLOADS["regex1g"]["bytes"]:
-                    with open(pmc_file) as f:
-                        pmc = json.load(f)
-                    if pmc.get("source_hash") == source_hash() and pmc.get("merges"):
-                        per_merge = pmc["hbm_bytes_total"] / pmc["merges"]
-                        phys = per_merge * num_merges * args.steps / (mg["ms"] * 1e-3) / 1e9
-                        roofline.update({
-                            "achieved": round(phys, 1), "frac": round(phys / HBM_PEAK_GBPS, 4),
-                            "traffic": int(per_merge * num_merges / max(mg["launches"] / args.steps, 1)),
-                            "achieved_kind": "physical ESTIMATE: HBM bytes per merge of the single-GPU PMC profile "
-                                             f"(profiles/{PROFILE_ROUND}_regex1g_pmc.json, same sources, same shard size) "
-                                             "x merges / this rank's hipEvent time of its merge passes",
-                            "equivalent_work_GBps": round(ach, 1)})
-        except Exception as e:
+        if args.dump_outputs and rank == 0:
+            dump_outputs(args.dump_outputs, res)
+        value_definition = (f"shard-merges per second = {world} ranks x the job's merges per second: every merge of the "
+                            f"ONE sharded job is applied to each rank's {wl['bytes']} B shard (weak scaling: the work per "
+                            "rank is fixed, the job grows with N); job_merges_per_s = the job's own rate")
+        if not args.full:  # the headline alone (the figures and checks beyond it: --full)
+            line.update({
+                "value": round(world * num_merges * args.steps / dt, 2), "ms_per_step": round(dt / args.steps * 1e3, 3),
+                "unit": "merges/s" if world == 1 else "shard-merges/s",
+                "job_merges_per_s": round(num_merges * args.steps / dt, 2),
+                "config": {"workload": f"{wl['desc']} sharded over {world} GPUs by contiguous chunk ranges, "
+                                       f"{wl['bytes']} B synthetic UTF-8 per GPU (seed {wl['seed']}+rank), vocab "
+                                       f"{wl['vocab']} ({num_merges} merges)",
+                           "parallelism": f"dp{world} ({dist_path})"},
+                "value_definition": value_definition, "roofline": None, "cpu_baseline": None,
+            })
+        else:
             roofline = None
-            line["roofline_error"] = f"{type(e).__name__}: {e}"
-        digest = int.from_bytes(hashlib.sha256(repr((res["pairs"], res["counts"], res["lens"])).encode())
-                                .digest()[:7], "big")
-        lo = torch.tensor([digest], dtype=torch.int64, device="cuda")
-        hi = lo.clone()
-        dist.all_reduce(lo, op=dist.ReduceOp.MIN)
-        dist.all_reduce(hi, op=dist.ReduceOp.MAX)
-        dp_check = {"ranks_agree": bool(lo.item() == hi.item()), "equals_single_gpu": None}
-        # the job's merges against the CPU oracle's: tests/golden/big_golden.json[regex1g_dp<world>_w] = the weighted
-        # oracle on the distinct chunks of the shards back to back (all 31,744 merges, pairs + counts + GLOBAL lengths);
-        # every rank vouches for its own shard's bytes (sha256), rank 0 compares the digests
-        g, mine = None, False
-        try:
-            g = golden_entry(f"{name}_dp{world}_w")
-            if world == 1:  # (BENCH_FORCE_DP: one shard = the single-GPU headline input)
-                g1 = golden_entry(f"{name}_w")
-                g = dict(g1, world=1, shard_sha256=[g1["data_sha256"]]) if g1 else None
-            if not (g and g.get("world") == world and g["bytes"] == wl["bytes"] and g["seed"] == wl["seed"]):
-                g = None
-            mine = bool(g) and hashlib.sha256(data).hexdigest() == g["shard_sha256"][rank]
-        except Exception:  # (a malformed entry: nothing is claimed; every rank still joins the reduction below)
+            try:
+                mg = eng.prof_read()["merge"]
+                eng.set_option("profile", 0)
+                n0 = torch.tensor([len(data)], dtype=torch.int64, device="cuda")
+                dist.all_reduce(n0, op=dist.ReduceOp.SUM)
+                lens = [int(n0.item())] + [int(x) for x in res["lens"]]  # GLOBAL stream lengths
+                alg = sum(4 * (2 * lens[i] + lens[i + 1]) for i in range(len(lens) - 1)) * args.steps / world
+                if mg["ms"] > 0 and mg["launches"]:
+                    ach = alg / (mg["ms"] * 1e-3) / 1e9
+                    roofline = {
+                        "bound": "hbm", "kernel": "merge pass of rank 0 on its shard: k_merge_chain | k_merge_chain_dense | "
+                                                 "k_merge_chain_dense1 (a chain step) | k_merge_ab_* + k_merge_aa (a general iteration)",
+                        "achieved": round(ach, 1), "peak": HBM_PEAK_GBPS, "unit": "GB/s",
+                        "frac": round(ach / HBM_PEAK_GBPS, 4), "traffic": None,
+                        "launches": mg["launches"], "avg_launch_ms": round(mg["ms"] / mg["launches"], 5),
+                        "alg_bytes_per_launch": int(alg // mg["launches"]),
+                        "achieved_kind": "algorithmic (SURVEY 8d bytes / hipEvent time)",
+                        "note": "per GPU: the job's algorithmic bytes (4(2N_i + N_{i+1}) on GLOBAL lengths) / world, over "
+                                "the hipEvent time of rank 0's merge passes",
+                    }
+                    # physical: counters cannot be read inside a run; a rank's merge passes work on a shard of the single-GPU
+                    # headline's size with the same kernels, so the committed single-GPU PMC profile's bytes per merge give
+                    # an ESTIMATE of this rank's traffic (labelled as such; the per-launch figure does not carry over:
+                    # a sharded step's batch is capped lower)
+                    pmc_file = os.path.join(ROOT, "profiles", f"{PROFILE_ROUND}_regex1g_pmc.json")
+                    if os.path.exists(pmc_file) and wl["bytes"] == WORKLOADS["regex1g"]["bytes"]:
+                        with open(pmc_file) as f:
+                            pmc = json.load(f)
+                        if pmc.get("source_hash") == source_hash() and pmc.get("merges"):
+                            per_merge = pmc["hbm_bytes_total"] / pmc["merges"]
+                            phys = per_merge * num_merges * args.steps / (mg["ms"] * 1e-3) / 1e9
+                            roofline.update({
+                                "achieved": round(phys, 1), "frac": round(phys / HBM_PEAK_GBPS, 4),
+                                "traffic": int(per_merge * num_merges / max(mg["launches"] / args.steps, 1)),
+                                "achieved_kind": "physical ESTIMATE: HBM bytes per merge of the single-GPU PMC profile "
+                                                 f"(profiles/{PROFILE_ROUND}_regex1g_pmc.json, same sources, same shard size) "
+                                                 "x merges / this rank's hipEvent time of its merge passes",
+                                "equivalent_work_GBps": round(ach, 1)})
+            except Exception as e:
+                roofline = None
+                line["roofline_error"] = f"{type(e).__name__}: {e}"
+            digest = int.from_bytes(hashlib.sha256(repr((res["pairs"], res["counts"], res["lens"])).encode())
+                                    .digest()[:7], "big")
+            lo = torch.tensor([digest], dtype=torch.int64, device="cuda")
+            hi = lo.clone()
+            dist.all_reduce(lo, op=dist.ReduceOp.MIN)
+            dist.all_reduce(hi, op=dist.ReduceOp.MAX)
+            dp_check = {"ranks_agree": bool(lo.item() == hi.item()), "equals_single_gpu": None}
+            # the job's merges against the CPU oracle's: tests/golden/big_golden.json[regex1g_dp<world>_w] = the weighted
+            # oracle on the distinct chunks of the shards back to back (all 31,744 merges, pairs + counts + GLOBAL lengths);
+            # every rank vouches for its own shard's bytes (sha256), rank 0 compares the digests
             g, mine = None, False
-        ok = torch.tensor([1 if mine else 0], dtype=torch.int64, device="cuda")
-        dist.all_reduce(ok, op=dist.ReduceOp.MIN)
-        if g is None:
-            dp_check["oracle"] = f"no committed oracle digest for {world} shard(s) of this size"
-        elif not bool(ok.item()):
-            dp_check["oracle"] = "not checked: a shard's bytes differ from the golden's"
-        elif rank == 0:
             try:
-                from helpers import checkpoint_digests, first_divergence
-                k = min(g["done"], len(res["pairs"]))
-                got = checkpoint_digests(res["pairs"][:k], res["counts"][:k], res["lens"][:k], g["step"])
-                bad = first_divergence(got, g["digests"])
-                checked = [c for c, _ in got if c in {c2 for c2, _ in g["digests"]}]
-                dp_check["oracle"] = {"entry": f"tests/golden/big_golden.json[{name}_dp{world}_w] (weighted oracle on the "
-                                               f"distinct chunks of the {world} shard(s) back to back, {g['done']} merges)",
-                                      "merges_checked": max(checked) if checked else 0,
-                                      "equal": bool(checked) and bad is None,
-                                      **({"first_bad_checkpoint": bad} if bad is not None else {})}
-            except Exception as e:
-                dp_check["oracle"] = f"not checked: {type(e).__name__}: {e}"
-        if rank == 0 and os.environ.get("BENCH_DP_CHECK", "1") == "1" and wl["bytes"] * world <= 2_000_000_000:
-            try:  # the sharded result must be the single-GPU result on the concatenation of all shards
-                parts, offl, base = [], [], 0
-                for r_ in range(world):
-                    d, o, _ = make_input(wl, r_)
-                    parts.append(d)
-                    offl.append(o + np.uint64(base))
-                    base += len(d)
-                eng2 = Engine(local_rank)
-                eng2.load_bytes(b"".join(parts), np.concatenate(offl))
-                single = eng2.train(num_merges)
-                eng2.close()
-                dp_check["equals_single_gpu"] = bool(
-                    single["pairs"] == res["pairs"] and single["counts"] == res["counts"]
-                    and single["lens"] == res["lens"])
-            except Exception as e:
-                dp_check["equals_single_gpu"] = f"not checked: {type(e).__name__}: {e}"
-        line.update({
-            # the units ALL ranks processed / the time (the bench contract's whole-job aggregate under weak scaling): a
-            # merge of the job is applied to every rank's 1 GB shard, so N ranks do N x num_merges shard-merges per train;
-            # the job's own rate (what a user waits for) is job_merges_per_s
-            "value": round(world * num_merges * args.steps / dt, 2), "ms_per_step": round(dt / args.steps * 1e3, 3),
-            # (N > 1: `value` counts a merge once per shard it is applied to -- the unit says so, so that nobody reads an
-            # N-fold rise of the job's own rate into it; at N = 1 the two are one and the unit is plain merges/s)
-            "unit": "merges/s" if world == 1 else "shard-merges/s",
-            "job_merges_per_s": round(num_merges * args.steps / dt, 2),
-            "config": {"workload": f"{wl['desc']} sharded over {world} GPUs by contiguous chunk ranges, "
-                                   f"{wl['bytes']} B synthetic UTF-8 per GPU (seed {wl['seed']}+rank), vocab "
-                                   f"{wl['vocab']} ({num_merges} merges); ranks agree: {dp_check['ranks_agree']}",
-                       "parallelism": f"dp{world} ({dist_path}: per step of 1..K merges one MIN all-reduce of a tie's "
-                                      f"first occurrences and one SUM all-reduce of the batch's table deltas)"},
-            "value_definition": f"shard-merges per second = {world} ranks x the job's merges per second: every merge of the "
-                                f"ONE sharded job is applied to each rank's {wl['bytes']} B shard (weak scaling: the work per "
-                                "rank is fixed, the job grows with N); job_merges_per_s = the job's own rate",
-            "sharded_check": dp_check, "roofline": roofline, "cpu_baseline": None,
-            "merge_passes": eng.train_stats(),
-        })
-        if rank == 0 and args.cpu_iters > 0:  # (rank 0's host, its own shard as the sample, scaled to the whole job)
-            try:
-                line["cpu_baseline"] = cpu_baseline(wl, data, offs, res, args.cpu_bytes, args.cpu_iters,
-                                                    total_bytes=wl["bytes"] * world)
-                # (its `value` is the CPU's rate on the WHOLE job in the job's merges per second: set it against
-                # job_merges_per_s, or times N against `value`)
-                line["cpu_baseline"]["compare_with"] = "job_merges_per_s"
-            except Exception as e:
-                line["cpu_baseline"] = f"failed: {type(e).__name__}: {e}"
+                g = golden_entry(f"{name}_dp{world}_w")
+                if world == 1:  # (BENCH_FORCE_DP: one shard = the single-GPU headline input)
+                    g1 = golden_entry(f"{name}_w")
+                    g = dict(g1, world=1, shard_sha256=[g1["data_sha256"]]) if g1 else None
+                if not (g and g.get("world") == world and g["bytes"] == wl["bytes"] and g["seed"] == wl["seed"]):
+                    g = None
+                mine = bool(g) and hashlib.sha256(data).hexdigest() == g["shard_sha256"][rank]
+            except Exception:  # (a malformed entry: nothing is claimed; every rank still joins the reduction below)
+                g, mine = None, False
+            ok = torch.tensor([1 if mine else 0], dtype=torch.int64, device="cuda")
+            dist.all_reduce(ok, op=dist.ReduceOp.MIN)
+            if g is None:
+                dp_check["oracle"] = f"no committed oracle digest for {world} shard(s) of this size"
+            elif not bool(ok.item()):
+                dp_check["oracle"] = "not checked: a shard's bytes differ from the golden's"
+            elif rank == 0:
+                try:
+                    from helpers import checkpoint_digests, first_divergence
+                    k = min(g["done"], len(res["pairs"]))
+                    got = checkpoint_digests(res["pairs"][:k], res["counts"][:k], res["lens"][:k], g["step"])
+                    bad = first_divergence(got, g["digests"])
+                    checked = [c for c, _ in got if c in {c2 for c2, _ in g["digests"]}]
+                    dp_check["oracle"] = {"entry": f"tests/golden/big_golden.json[{name}_dp{world}_w] (weighted oracle on the "
+                                                   f"distinct chunks of the {world} shard(s) back to back, {g['done']} merges)",
+                                          "merges_checked": max(checked) if checked else 0,
+                                          "equal": bool(checked) and bad is None,
+                                          **({"first_bad_checkpoint": bad} if bad is not None else {})}
+                except Exception as e:
+                    dp_check["oracle"] = f"not checked: {type(e).__name__}: {e}"
+            if rank == 0 and os.environ.get("BENCH_DP_CHECK", "1") == "1" and wl["bytes"] * world <= 2_000_000_000:
+                try:  # the sharded result must be the single-GPU result on the concatenation of all shards
+                    parts, offl, base = [], [], 0
+                    for r_ in range(world):
+                        d, o, _ = make_input(wl, r_)
+                        parts.append(d)
+                        offl.append(o + np.uint64(base))
+                        base += len(d)
+                    eng2 = Engine(local_rank)
+                    eng2.load_bytes(b"".join(parts), np.concatenate(offl))
+                    single = eng2.train(num_merges)
+                    eng2.close()
+                    dp_check["equals_single_gpu"] = bool(
+                        single["pairs"] == res["pairs"] and single["counts"] == res["counts"]
+                        and single["lens"] == res["lens"])
+                except Exception as e:
+                    dp_check["equals_single_gpu"] = f"not checked: {type(e).__name__}: {e}"
+            line.update({
+                # the units ALL ranks processed / the time (the bench contract's whole-job aggregate under weak scaling): a
+                # merge of the job is applied to every rank's 1 GB shard, so N ranks do N x num_merges shard-merges per train;
+                # the job's own rate (what a user waits for) is job_merges_per_s
+                "value": round(world * num_merges * args.steps / dt, 2), "ms_per_step": round(dt / args.steps * 1e3, 3),
+                # (N > 1: `value` counts a merge once per shard it is applied to -- the unit says so, so that nobody reads an
+                # N-fold rise of the job's own rate into it; at N = 1 the two are one and the unit is plain merges/s)
+                "unit": "merges/s" if world == 1 else "shard-merges/s",
+                "job_merges_per_s": round(num_merges * args.steps / dt, 2),
+                "config": {"workload": f"{wl['desc']} sharded over {world} GPUs by contiguous chunk ranges, "
+                                       f"{wl['bytes']} B synthetic UTF-8 per GPU (seed {wl['seed']}+rank), vocab "
+                                       f"{wl['vocab']} ({num_merges} merges); ranks agree: {dp_check['ranks_agree']}",
+                           "parallelism": f"dp{world} ({dist_path}: per step of 1..K merges one MIN all-reduce of a tie's "
+                                          f"first occurrences and one SUM all-reduce of the batch's table deltas)"},
+                "value_definition": value_definition,
+                "sharded_check": dp_check, "roofline": roofline, "cpu_baseline": None,
+                "merge_passes": eng.train_stats(),
+            })
+            if rank == 0 and args.cpu_iters > 0:  # (rank 0's host, its own shard as the sample, scaled to the whole job)
+                try:
+                    line["cpu_baseline"] = cpu_baseline(wl, data, offs, res, args.cpu_bytes, args.cpu_iters,
+                                                        total_bytes=wl["bytes"] * world)
+                    # (its `value` is the CPU's rate on the WHOLE job in the job's merges per second: set it against
+                    # job_merges_per_s, or times N against `value`)
+                    line["cpu_baseline"]["compare_with"] = "job_merges_per_s"
+                except Exception as e:
+                    line["cpu_baseline"] = f"failed: {type(e).__name__}: {e}"
 
     bad = parity_failures(line)
     if bad:

@@ -125,3 +125,59 @@ def first_divergence(got, want):
         if k in want_d and want_d[k] != d:
             return k
     return None
+
+
+# The inputs of the comparisons with the reference's recorded answers (tests/golden/live_reference.json,
+# written by tests/golden/gen_live_reference.py): rebuilt here at test time, pinned there by sha256.
+
+def random_texts(native):
+    """tie-heavy alphabets, runs, multi-byte text"""
+    import random
+    rng = random.Random(424242)
+    texts = []
+    for k, n in [(2, 400), (3, 900), (5, 1500), (26, 2500)]:
+        texts.append("".join(rng.choice([chr(97 + rng.randrange(k)), " ", chr(97 + rng.randrange(k))]) for _ in range(n)))
+    texts.append("aaaa" * 50 + " " + "ab" * 80 + "   \n\n" + "aaa " * 40)
+    texts.append(native.synth_text(6000, 99).decode())
+    return texts
+
+
+def tie_heavy_texts(native):
+    import random
+    rng = random.Random(77)
+    texts = []
+    for k, n in [(2, 3000), (3, 5000), (6, 8000)]:
+        words = ["".join(chr(97 + rng.randrange(k)) for _ in range(rng.randrange(1, 6))) for _ in range(30)]
+        texts.append(" ".join(rng.choice(words) for _ in range(n)))
+    texts.append("aaaa " * 40 + "ab ab  ab\n\n" * 30 + "aaaa" * 9 + " x")
+    texts.append(native.synth_text(300_000, 31).decode())
+    return texts
+
+
+def weighted_texts(native):
+    return tie_heavy_texts(native)[:4] + [native.synth_text(40_000, 33).decode()]
+
+
+def cl100k_probe(native):
+    return native.synth_text(30_000, 52).decode() + " don't  stop 12345 ünïcödé 😉"
+
+
+def cl100k_base_pairs(native):
+    """the merge list the cl100k-sized tables are built around (the weighted oracle, 3000 merges)"""
+    import oracle
+    data, offs = split_chunks(native.synth_text(400_000, 51).decode())
+    d2, o2, wts, _ = oracle.dedup(data, offs)
+    return oracle.train(d2, 3000, o2, weights=wts)[0]
+
+
+def saved_files_text(golden_dir):
+    """train.py's flow on a slice of the reference's sample text, with control characters and a lone byte"""
+    import os
+    text = open(os.path.join(golden_dir, "taylorswift.txt"), encoding="utf-8").read()[:40_000]
+    return text + "\x00\x07 control ​ chars � and a lone \x80 byte".encode(
+        "utf-8", "surrogatepass").decode("utf-8", "replace")
+
+
+def sha256_text(text):
+    import hashlib
+    return hashlib.sha256(text.encode("utf-8")).hexdigest()

@@ -211,7 +211,7 @@ def test_run_train_workload_assembles_its_line_on_a_test_double(secondary, mode)
 
 
 def test_main_prints_one_conforming_line_at_n1_on_a_test_double(monkeypatch, capsys):
-    """bench.main() at N = 1 (a small --bytes / --vocab, no secondaries) with the engine replaced by the test double:
+    """bench.main() --full at N = 1 (a small --bytes / --vocab, no secondaries) with the engine replaced by the test double:
     the keys the driver's contract names are there, the CPU baseline leg runs, the line is one JSON object."""
     import torch
     import minbpe_amd
@@ -227,7 +227,7 @@ def test_main_prints_one_conforming_line_at_n1_on_a_test_double(monkeypatch, cap
     monkeypatch.setattr(torch.cuda, "synchronize", lambda *a, **k: None)
     monkeypatch.setattr(minbpe_amd, "Engine", Double)
     monkeypatch.setattr(sys, "argv", ["bench.py", "--bytes", "50000", "--vocab", str(256 + 30), "--steps", "2", "--warmup", "1",
-                                      "--cpu-iters", "3", "--cpu-bytes", "20000"])
+                                      "--cpu-iters", "3", "--cpu-bytes", "20000", "--full"])
     for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "BENCH_FORCE_DP"):
         monkeypatch.delenv(k, raising=False)
     bench.main()
@@ -249,3 +249,115 @@ def test_main_prints_one_conforming_line_at_n1_on_a_test_double(monkeypatch, cap
     assert len(line["config"]["workload"]) < 120 and line["config"]["workload"].startswith("parity")
     assert line["config"]["parity_equal"] is None and "parity_failures" not in line
     assert line["secondary"] == {}
+
+
+class _CountingDouble(_BenchDouble):
+    """the test double of bench.main(), counting its train() calls and keeping the options it is given (`opts`,
+    `options_set`).  Call k (from 1) returns the oracle's merges with every token id raised by PAIR_SHIFT * k, so
+    that a dump shows which call it came from (a == b stays a == b: the invariants still hold)."""
+    PAIR_SHIFT = 1000
+    trains = 0
+    last = None
+
+    def __init__(self, device=0):
+        super().__init__()
+        self.options_set = []
+        type(self).last = self
+
+    def set_option(self, k, v):
+        self.options_set.append((k, v))
+        super().set_option(k, v)
+
+    def train(self, n):
+        type(self).trains += 1
+        res = super().train(n)
+        d = self.PAIR_SHIFT * type(self).trains
+        return dict(res, pairs=[(a + d, b + d) for a, b in res["pairs"]])
+
+    def close(self):
+        pass
+
+
+def _main_on_double(monkeypatch, capsys, argv):
+    import torch
+    import minbpe_amd
+    _CountingDouble.trains = 0
+    monkeypatch.setattr(torch.cuda, "set_device", lambda *a, **k: None)
+    monkeypatch.setattr(torch.cuda, "synchronize", lambda *a, **k: None)
+    monkeypatch.setattr(minbpe_amd, "Engine", _CountingDouble)
+    monkeypatch.setattr(sys, "argv", ["bench.py"] + argv)
+    for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "BENCH_FORCE_DP"):
+        monkeypatch.delenv(k, raising=False)
+    bench.main()
+    out = [ln for ln in capsys.readouterr().out.splitlines() if ln.strip()]
+    assert len(out) == 1
+    return json.loads(out[0])
+
+
+def test_plain_run_times_only_its_steps_and_dumps_the_last_one(monkeypatch, capsys, tmp_path):
+    """bench.py without --full: warm-up + the timed steps and nothing else (no breakdown step, no step without event
+    records, no CPU baseline, no parity check, no event records: the profile option is never set); --dump-outputs
+    writes the merges of the last timed step -- the last of the 2 + 3 calls -- as float64 arrays, the same on every
+    run with the same arguments"""
+    import numpy as np
+    from fake_engine import OracleEngine
+    argv = ["--gpus", "1", "--bytes", "50000", "--vocab", str(256 + 30), "--steps", "3", "--warmup", "2"]
+    dumps = []
+    for i in range(2):
+        d = tmp_path / f"run{i}"
+        line = _main_on_double(monkeypatch, capsys, argv + ["--dump-outputs", str(d)])
+        assert _CountingDouble.trains == 2 + 3
+        assert not any(k == "profile" for k, _ in _CountingDouble.last.options_set)
+        dumps.append({k: np.load(d / f"{k}.npy") for k in ("pairs", "counts", "lens")})
+    for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling",
+              "vs_baseline", "dtype", "data", "config"):
+        assert k in line, k
+    assert line["metric"] == "BPE merges/sec" and line["unit"] == "merges/s" and line["higher_is_better"] is True
+    assert line["dtype"] == "int32" and line["steps"] == 3 and line["warmup"] == 2
+    assert line["value"] == pytest.approx(30 / (line["ms_per_step"] * 1e-3), rel=1e-3)
+    assert line["roofline"] is None and line["cpu_baseline"] is None and "secondary" not in line
+    assert "parity" not in line and "invariants" not in line and len(line["config"]["workload"]) < 120
+    a, b = dumps
+    for k in a:
+        assert a[k].dtype == np.float64 and np.array_equal(a[k], b[k]), k
+    assert a["pairs"].shape == (30, 2) and a["counts"].shape == a["lens"].shape == (30,)
+    # what train() returns on this input
+    wl = dict(bench.WORKLOADS["regex1g"], bytes=50000, vocab=256 + 30)
+    data, offs, _ = bench.make_input(wl)
+    eng = OracleEngine()
+    eng.load_bytes(data, offs)
+    want = eng.train(30)
+    last = _CountingDouble.PAIR_SHIFT * (2 + 3)  # (the 5th call: the last timed step)
+    assert a["pairs"].astype(np.int64).tolist() == [[x + last, y + last] for x, y in want["pairs"]]
+    assert a["counts"].astype(np.int64).tolist() == list(want["counts"])
+    assert a["lens"].astype(np.int64).tolist() == list(want["lens"])
+
+
+def test_full_run_keeps_its_extra_steps(monkeypatch, capsys, tmp_path):
+    """--full: the breakdown step before the timed steps and the step without event records after them, as before,
+    with event records in the timed steps; --dump-outputs still writes the last TIMED step's outputs (the 6th of the
+    2 + 1 + 3 + 1 calls, not the untimed one after it)"""
+    import numpy as np
+    from fake_engine import OracleEngine
+    argv = ["--gpus", "1", "--bytes", "50000", "--vocab", str(256 + 30), "--steps", "3", "--warmup", "2",
+            "--cpu-iters", "0", "--full", "--dump-outputs", str(tmp_path)]
+    line = _main_on_double(monkeypatch, capsys, argv)
+    assert _CountingDouble.trains == 2 + 1 + 3 + 1
+    assert [v for k, v in _CountingDouble.last.options_set if k == "profile"] == [2, 1, 0]
+    assert line["config"]["parity_equal"] is None and line["config"]["invariants_hold"] is True
+    assert line["roofline"]["bound"] == "hbm" and line["secondary"] == {}
+    pairs = np.load(tmp_path / "pairs.npy").astype(np.int64)
+    assert pairs.shape == (30, 2)
+    wl = dict(bench.WORKLOADS["regex1g"], bytes=50000, vocab=256 + 30)
+    data, offs, _ = bench.make_input(wl)
+    eng = OracleEngine()
+    eng.load_bytes(data, offs)
+    last = _CountingDouble.PAIR_SHIFT * (2 + 1 + 3)
+    assert pairs.tolist() == [[x + last, y + last] for x, y in eng.train(30)["pairs"]]
+
+
+def test_secondary_workloads_need_full(monkeypatch, capsys):
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--secondary", "cfg2"])
+    with pytest.raises(SystemExit) as e:
+        bench.main()
+    assert e.value.code == 2 and "--full" in capsys.readouterr().err

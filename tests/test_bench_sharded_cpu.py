@@ -129,7 +129,7 @@ def _worker(rank, world, port, argv, out_q, tmpdir, golden=None, path="steps"):
 def test_sharded_bench_leg_runs_on_doubles_at_world_2(tmp_path, golden, path):
     world = 2
     argv = ["--gpus", str(world), "--bytes", "40000", "--vocab", str(256 + 24), "--steps", "1", "--warmup", "1",
-            "--cpu-iters", "3", "--cpu-bytes", "20000"]
+            "--cpu-iters", "3", "--cpu-bytes", "20000", "--full"]
     g = None
     if golden != "none":
         g = _tiny_job_golden(world, 40000, 2, 24)  # (bench.py's regex1g workload: seed 2 + rank)
@@ -170,3 +170,41 @@ def test_sharded_bench_leg_runs_on_doubles_at_world_2(tmp_path, golden, path):
     assert line["roofline"]["bound"] == "hbm" and line["roofline"]["frac"] > 0
     cpu = line["cpu_baseline"]
     assert cpu["kind"] == "port" and cpu["cores"] == 1 and cpu["compare_with"] == "job_merges_per_s"
+
+
+@pytest.mark.timeout(600)
+def test_sharded_bench_plain_run_at_world_2_dumps_its_outputs(tmp_path):
+    """bench.py --gpus 2 without --full: the headline alone (no checks, no CPU baseline), and --dump-outputs writes
+    the job's merges from rank 0 -- the merges the oracle makes on the shards back to back"""
+    import numpy as np
+    world = 2
+    out_dir = tmp_path / "outputs"
+    argv = ["--gpus", str(world), "--bytes", "40000", "--vocab", str(256 + 24), "--steps", "2", "--warmup", "1",
+            "--dump-outputs", str(out_dir)]
+    ctx = mp.get_context("spawn")
+    q = ctx.Queue()
+    port = _free_port()
+    procs = [ctx.Process(target=_worker, args=(r, world, port, argv, q, str(tmp_path), None, "steps")) for r in range(world)]
+    for p in procs:
+        p.start()
+    outs = sorted(q.get(timeout=500) for _ in procs)
+    for p in procs:
+        p.join(timeout=60)
+    for rank, status, text in outs:
+        assert status == "ok", f"rank {rank}: {status}: {text}"
+    assert outs[1][2].strip() == ""
+    lines = [ln for ln in outs[0][2].splitlines() if ln.strip()]
+    assert len(lines) == 1
+    line = json.loads(lines[0])
+    assert line["n_gpus"] == world and line["unit"] == "shard-merges/s" and line["steps"] == 2 and line["warmup"] == 1
+    assert line["value"] == pytest.approx(world * line["job_merges_per_s"], rel=1e-3)
+    assert line["job_merges_per_s"] == pytest.approx(24 / (line["ms_per_step"] * 1e-3), rel=1e-3)
+    assert "sharded_check" not in line and line["roofline"] is None and line["cpu_baseline"] is None
+    pairs, counts, lens = (np.load(out_dir / f"{k}.npy") for k in ("pairs", "counts", "lens"))
+    assert pairs.dtype == counts.dtype == lens.dtype == np.float64
+    assert pairs.shape == (24, 2) and counts.shape == lens.shape == (24,)
+    g = _tiny_job_golden(world, 40000, 2, 24)
+    from helpers import checkpoint_digests
+    got = checkpoint_digests(pairs.astype(np.int64).tolist(), counts.astype(np.int64).tolist(),
+                             lens.astype(np.int64).tolist(), g["step"])
+    assert got[-1] == list(g["digests"][-1])

@@ -1,16 +1,25 @@
 """CPU: pins the oracle (oracle/bpe_oracle.c) against vectors produced by the
-reference itself (tests/golden/golden.json <- gen_golden.py) and, when the
-reference tree is present (build container only), against the live reference
-on tests/taylorswift.txt (hashes of SURVEY.md section 8c)."""
+reference itself (tests/golden/golden.json <- gen_golden.py) and against the
+reference's recorded answers on further inputs (tests/golden/live_reference.json
+<- gen_live_reference.py), tests/golden/taylorswift.txt among them (hashes of
+SURVEY.md section 8c)."""
 import hashlib
+import json
 import os
-import sys
-import types
 
 import pytest
 
 import oracle
 from helpers import case_text, data_for
+
+GOLDEN_DIR = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
+
+
+@pytest.fixture(scope="module")
+def live_ref():
+    """what the reference answered on the inputs below (tests/golden/gen_live_reference.py)"""
+    with open(os.path.join(GOLDEN_DIR, "live_reference.json"), encoding="utf-8") as f:
+        return json.load(f)
 
 
 def test_train_cases(golden, native):
@@ -62,14 +71,8 @@ def test_wikipedia_known_answer():
     assert ids.tolist() == [258, 100, 258, 97, 99]
 
 
-REF = "/root/reference"
-
-
-@pytest.mark.skipif(not os.path.isdir(REF), reason="reference tree only exists in the build container")
-def test_against_live_reference_taylorswift(golden, monkeypatch):
-    monkeypatch.setitem(sys.modules, "tiktoken", types.ModuleType("tiktoken"))
-    sys.path.insert(0, REF)
-    text = open(os.path.join(REF, "tests", "taylorswift.txt"), encoding="utf-8").read()
+def test_against_live_reference_taylorswift(golden):
+    text = open(os.path.join(GOLDEN_DIR, "taylorswift.txt"), encoding="utf-8").read()
     g = golden["taylorswift"]
     assert hashlib.sha256(text.encode()).hexdigest().startswith(g["sha256_prefix"])
 
@@ -91,31 +94,18 @@ def test_against_live_reference_taylorswift(golden, monkeypatch):
     assert len(ids) == g["regex512_encode_len"] and h(ids.tolist()) == g["regex512_encode_hash"]
 
 
-@pytest.mark.skipif(not os.path.isdir(REF), reason="reference tree only exists in the build container")
-def test_against_live_reference_random(native, monkeypatch):
-    """Differential check: the reference itself (imported from its read-only tree) against the
-    oracle on random inputs -- tie-heavy alphabets, runs, multi-byte text, special tokens."""
-    import random
-    monkeypatch.setitem(sys.modules, "tiktoken", types.ModuleType("tiktoken"))
-    if REF not in sys.path:
-        sys.path.insert(0, REF)
-    from minbpe import BasicTokenizer as RefBasic, RegexTokenizer as RefRegex
-    from helpers import split_chunks
-    rng = random.Random(424242)
-    texts = []
-    for k, n in [(2, 400), (3, 900), (5, 1500), (26, 2500)]:
-        texts.append("".join(rng.choice([chr(97 + rng.randrange(k)), " ", chr(97 + rng.randrange(k))]) for _ in range(n)))
-    texts.append("aaaa" * 50 + " " + "ab" * 80 + "   \n\n" + "aaa " * 40)
-    texts.append(native.synth_text(6000, 99).decode())
-    for text in texts:
+def test_against_live_reference_random(native, live_ref):
+    """Differential check: the reference's recorded answers against the oracle on random inputs --
+    tie-heavy alphabets, runs, multi-byte text, special tokens."""
+    from helpers import random_texts, sha256_text, split_chunks
+    rows = iter(live_ref["random"])
+    n = 0
+    for text in random_texts(native):
         for nm in (5, 40):
+            row = next(rows)
+            assert row["sha256"] == sha256_text(text) and row["num_merges"] == nm
             # BasicTokenizer (basic.py:20-49, 57-74)
-            ref = RefBasic()
-            try:
-                ref.train(text, 256 + nm)
-                ref_pairs = list(ref.merges)
-            except ValueError:
-                ref_pairs = None
+            ref_pairs = None if row["basic"] is None else [tuple(p) for p in row["basic"]]
             if ref_pairs is None:
                 with pytest.raises(oracle.OracleEmptyStats):
                     oracle.train(text.encode(), nm)
@@ -123,15 +113,10 @@ def test_against_live_reference_random(native, monkeypatch):
                 pairs, _, _ = oracle.train(text.encode(), nm)
                 assert pairs == ref_pairs
                 probe = text[: len(text) // 3] + text[::-1][:50]
-                assert oracle.encode(pairs, probe.encode())[0].tolist() == ref.encode(probe)
+                assert oracle.encode(pairs, probe.encode())[0].tolist() == row["basic_probe_ids"]
             # RegexTokenizer (regex.py:36-70, 92-121)
-            ref = RefRegex()
             data, offs = split_chunks(text)
-            try:
-                ref.train(text, 256 + nm)
-                ref_pairs = list(ref.merges)
-            except ValueError:
-                ref_pairs = None
+            ref_pairs = None if row["regex"] is None else [tuple(p) for p in row["regex"]]
             if ref_pairs is None:
                 with pytest.raises(oracle.OracleEmptyStats):
                     oracle.train(data, nm, offs)
@@ -140,7 +125,9 @@ def test_against_live_reference_random(native, monkeypatch):
                 assert pairs == ref_pairs
                 probe = text[: len(text) // 3]
                 pd, po = split_chunks(probe)
-                assert oracle.encode(pairs, pd, po)[0].tolist() == ref.encode_ordinary(probe)
+                assert oracle.encode(pairs, pd, po)[0].tolist() == row["regex_probe_ids"]
+            n += 1
+    assert n == len(live_ref["random"]) == 12
 
 
 # ---------------------------------------------------------------------------------------------
@@ -148,22 +135,10 @@ def test_against_live_reference_random(native, monkeypatch):
 # makes the reference's answer computable for the 1 GB headline (all 31,744 merges in minutes instead of
 # days).  It must give what the plain loop gives on the un-de-duplicated list of chunks.
 
-def _tie_heavy_texts(native):
-    import random
-    rng = random.Random(77)
-    texts = []
-    for k, n in [(2, 3000), (3, 5000), (6, 8000)]:
-        words = ["".join(chr(97 + rng.randrange(k)) for _ in range(rng.randrange(1, 6))) for _ in range(30)]
-        texts.append(" ".join(rng.choice(words) for _ in range(n)))
-    texts.append("aaaa " * 40 + "ab ab  ab\n\n" * 30 + "aaaa" * 9 + " x")
-    texts.append(native.synth_text(300_000, 31).decode())
-    return texts
-
-
 def test_weighted_oracle_equals_plain_oracle(native):
     import numpy as np
-    from helpers import split_chunks
-    for text in _tie_heavy_texts(native):
+    from helpers import split_chunks, tie_heavy_texts
+    for text in tie_heavy_texts(native):
         data, offs = split_chunks(text)
         d2, o2, wts, first = oracle.dedup(data, offs)
         assert int(wts.sum()) == len(offs) and len(o2) == len(set(
@@ -199,30 +174,25 @@ def test_oracle_dedup_equals_library_dedup(native):
     assert order == want and [got[c] for c in order] == [int(w) for w in wts]
 
 
-@pytest.mark.skipif(not os.path.isdir(REF), reason="reference tree only exists in the build container")
-def test_weighted_oracle_against_live_reference(native, monkeypatch):
-    """RegexTokenizer.train of the reference itself on the full text vs the weighted oracle on the distinct
-    chunks: the same merges (regex.py:41-63)."""
-    monkeypatch.setitem(sys.modules, "tiktoken", types.ModuleType("tiktoken"))
-    if REF not in sys.path:
-        sys.path.insert(0, REF)
-    from minbpe import RegexTokenizer as RefRegex
-    from helpers import split_chunks
-    for text in _tie_heavy_texts(native)[:4] + [native.synth_text(40_000, 33).decode()]:
+def test_weighted_oracle_against_live_reference(native, live_ref):
+    """RegexTokenizer.train of the reference itself on the full text (its recorded merges) vs the weighted oracle
+    on the distinct chunks: the same merges (regex.py:41-63)."""
+    from helpers import sha256_text, split_chunks, weighted_texts
+    rows = iter(live_ref["weighted"])
+    n = 0
+    for text in weighted_texts(native):
         data, offs = split_chunks(text)
         d2, o2, wts, _ = oracle.dedup(data, offs)
         for nm in (8, 60):
-            ref = RefRegex()
-            try:
-                ref.train(text, 256 + nm)
-                ref_pairs = list(ref.merges)
-            except ValueError:
-                ref_pairs = None
-            if ref_pairs is None:
+            row = next(rows)
+            assert row["sha256"] == sha256_text(text) and row["num_merges"] == nm
+            if row["regex"] is None:
                 with pytest.raises(oracle.OracleEmptyStats):
                     oracle.train(d2, nm, o2, weights=wts)
             else:
-                assert oracle.train(d2, nm, o2, weights=wts)[0] == ref_pairs
+                assert oracle.train(d2, nm, o2, weights=wts)[0] == [tuple(p) for p in row["regex"]]
+            n += 1
+    assert n == len(live_ref["weighted"]) == 10
 
 
 def test_big_golden_weighted_entries_continue_the_plain_ones():
@@ -241,30 +211,21 @@ def test_big_golden_weighted_entries_continue_the_plain_ones():
     assert big["regex1g_w"]["done"] == 31744
 
 
-@pytest.mark.skipif(not os.path.isdir(REF), reason="reference tree only exists in the build container")
-def test_oracle_encode_with_a_cl100k_sized_table_against_live_reference(native, monkeypatch):
+def test_oracle_encode_with_a_cl100k_sized_table_against_live_reference(native, live_ref):
     """oracle.encode with 100,000 ranks -- ids 256 + rank up to 100,255, and a merges dict whose values are
-    not consecutive (what GPT4Tokenizer's are) -- against the reference's own _encode_chunk
-    (regex.py:92-121) given the same merges dict."""
-    import numpy as np
-    monkeypatch.setitem(sys.modules, "tiktoken", types.ModuleType("tiktoken"))
-    if REF not in sys.path:
-        sys.path.insert(0, REF)
-    from minbpe import RegexTokenizer as RefRegex
-    from helpers import cl100k_shaped_table, split_chunks
-    text = native.synth_text(400_000, 51).decode()
-    data, offs = split_chunks(text)
-    d2, o2, wts, _ = oracle.dedup(data, offs)
-    base = oracle.train(d2, 3000, o2, weights=wts)[0]
-    probe = native.synth_text(30_000, 52).decode() + " don't  stop 12345 ünïcödé 😉"
+    not consecutive (what GPT4Tokenizer's are) -- against what the reference's own _encode_chunk
+    (regex.py:92-121) answered given the same merges dict."""
+    from helpers import cl100k_base_pairs, cl100k_probe, cl100k_shaped_table, sha256_text, split_chunks
+    rec = live_ref["cl100k_encode"]
+    base = cl100k_base_pairs(native)
+    assert sha256_text(repr([tuple(p) for p in base])) == rec["base_pairs_sha256"]
+    probe = cl100k_probe(native)
+    assert sha256_text(probe) == rec["probe_sha256"]
     pd, po = split_chunks(probe)
     for kind in ("rank", "sparse"):
         pairs, mids = cl100k_shaped_table(base, 100_000, 5, kind)
-        ref = RefRegex()
-        vals = mids if mids is not None else 256 + np.arange(len(pairs))
-        ref.merges = {(int(a), int(b)): int(v) for (a, b), v in zip(pairs, vals)}
-        assert len(ref.merges) == len(pairs)  # (the table has no repeated pair)
-        want = ref.encode_ordinary(probe)
+        assert len({(int(a), int(b)) for a, b in pairs}) == len(pairs)  # (the table has no repeated pair)
+        want = rec[kind]
         got, _ = oracle.encode(pairs, pd, po, merge_ids=mids)
         assert got.tolist() == want
         assert max(want) >= 65536 and len(set(want)) > 500

@@ -1,74 +1,100 @@
-"""CPU, build container only: the reference's OWN test module (tests/test_tokenizer.py, read from
-its read-only tree at run time, never copied) executed with `minbpe` resolving to this package.
-The device engine is the oracle-backed test double (tests/fake_engine.py), so this exercises the
-drop-in surface -- names, signatures, results, exceptions, save/load -- not the kernels; the two
-tiktoken-equality tests are left out (no cl100k ranks offline)."""
-import importlib.util
+"""CPU: the checks of the reference's OWN test module (tests/test_tokenizer.py) restated on its data -- test
+strings, the Wikipedia example, save/load with and without special tokens -- with `minbpe` resolving to this
+package, and compared with what the reference itself answered on the same data (tests/golden/live_reference.json
+<- tests/golden/gen_live_reference.py).  The device engine is the oracle-backed test double
+(tests/fake_engine.py), so this exercises the drop-in surface -- names, signatures, results, exceptions,
+save/load -- not the kernels; the two tiktoken-equality tests are left out (no cl100k ranks offline)."""
+import json
 import os
 import sys
-import types
 
 import pytest
 
-REF = "/root/reference"
+GOLDEN_DIR = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
 
 
-@pytest.mark.skipif(not os.path.isdir(REF), reason="reference tree only exists in the build container")
-def test_reference_test_module_passes_against_this_package(native, monkeypatch, tmp_path):
+@pytest.fixture(scope="module")
+def live_ref():
+    with open(os.path.join(GOLDEN_DIR, "live_reference.json"), encoding="utf-8") as f:
+        return json.load(f)
+
+
+def test_reference_test_module_passes_against_this_package(native, monkeypatch, tmp_path, live_ref):
     import minbpe_amd
     import minbpe_amd.tokenizer as T
     from fake_engine import OracleEngine
     eng = OracleEngine()
     monkeypatch.setattr(T, "engine", lambda device=None: eng)
     monkeypatch.setitem(sys.modules, "minbpe", minbpe_amd)  # `from minbpe import BasicTokenizer, ...`
-    monkeypatch.setitem(sys.modules, "tiktoken", types.ModuleType("tiktoken"))
-    spec = importlib.util.spec_from_file_location("ref_test_tokenizer", os.path.join(REF, "tests", "test_tokenizer.py"))
-    ref = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(ref)
-    assert ref.BasicTokenizer is minbpe_amd.BasicTokenizer and ref.RegexTokenizer is minbpe_amd.RegexTokenizer
+    from minbpe import BasicTokenizer, RegexTokenizer
+    assert BasicTokenizer is minbpe_amd.BasicTokenizer and RegexTokenizer is minbpe_amd.RegexTokenizer
+    suite = live_ref["suite"]
+    texts = list(suite["test_strings"])
+    for name in suite["test_files"]:  # the module's FILE: strings, resolved next to its test file
+        texts.append(open(os.path.join(GOLDEN_DIR, name), encoding="utf-8").read())
+    assert len(texts) == 4
     ran = 0
-    for factory in (ref.BasicTokenizer, ref.RegexTokenizer):
-        for text in ref.test_strings:  # includes FILE:taylorswift.txt, resolved next to the reference's test file
-            ref.test_encode_decode_identity(factory, text)
+    for name, factory in (("basic", BasicTokenizer), ("regex", RegexTokenizer)):
+        for text in texts:  # test_encode_decode_identity
+            tok = factory()
+            assert tok.decode(tok.encode(text)) == text
             ran += 1
-        ref.test_wikipedia_example(factory)
+        tok = factory()  # test_wikipedia_example
+        tok.train("aaabdaaabac", 256 + 3)
+        ids = tok.encode("aaabdaaabac")
+        assert ids == [258, 100, 258, 97, 99] == suite["wikipedia"][name]
+        assert tok.decode(tok.encode("aaabdaaabac")) == "aaabdaaabac"
         ran += 1
     monkeypatch.chdir(tmp_path)  # test_save_load writes its files into the working directory
-    for specials in ({}, ref.special_tokens):
-        ref.test_save_load(specials)
+    text = suite["llama_text"]
+    for rec in suite["save_load"]:  # test_save_load
+        specials = rec["special_tokens"]
+        tok = RegexTokenizer()
+        tok.train(text, 256 + 64)
+        tok.register_special_tokens(specials)
+        assert tok.decode(tok.encode(text, "all")) == text
+        ids = tok.encode(text, "all")
+        assert ids == rec["ids"]  # the reference's own encoding
+        tok.save("test_tokenizer_tmp")
+        assert open("test_tokenizer_tmp.model", encoding="utf-8").read() == rec["model"]
+        tok = RegexTokenizer()
+        tok.load("test_tokenizer_tmp.model")
+        assert tok.decode(ids) == text
+        assert tok.decode(tok.encode(text, "all")) == text
+        assert tok.encode(text, "all") == ids
+        for f in ("test_tokenizer_tmp.model", "test_tokenizer_tmp.vocab"):
+            os.remove(f)
         ran += 1
+    assert [r["special_tokens"] for r in suite["save_load"]][0] == {} and len(suite["save_load"]) == 2
     assert ran == 12 and os.listdir(tmp_path) == []
 
 
-@pytest.mark.skipif(not os.path.isdir(REF), reason="reference tree only exists in the build container")
-def test_saved_files_are_byte_identical_to_the_reference(native, monkeypatch, tmp_path):
+def test_saved_files_are_byte_identical_to_the_reference(native, monkeypatch, tmp_path, live_ref):
     """train.py's flow (train, register specials, save) on a slice of the reference's own sample
-    text: the .model and .vocab files written by this package and by the reference are the same bytes."""
+    text: the .model and .vocab files written by this package are the bytes the reference wrote."""
     import minbpe_amd.tokenizer as T
     from fake_engine import OracleEngine
+    from helpers import saved_files_text, sha256_text
     eng = OracleEngine()
     monkeypatch.setattr(T, "engine", lambda device=None: eng)
-    monkeypatch.setitem(sys.modules, "tiktoken", types.ModuleType("tiktoken"))
-    monkeypatch.syspath_prepend(REF)
-    import minbpe as ref
-    text = open(os.path.join(REF, "tests", "taylorswift.txt"), encoding="utf-8").read()[:40_000]
-    text += "\x00\x07 control ​ chars � and a lone \x80 byte".encode("utf-8", "surrogatepass").decode("utf-8", "replace")
-    for name, ours, theirs in (("basic", T.BasicTokenizer, ref.BasicTokenizer),
-                               ("regex", T.RegexTokenizer, ref.RegexTokenizer)):
-        a, b = ours(), theirs()
+    text = saved_files_text(GOLDEN_DIR)
+    saved = live_ref["saved_files"]
+    assert sha256_text(text) == saved["sha256"]
+    for name, ours in (("basic", T.BasicTokenizer), ("regex", T.RegexTokenizer)):
+        theirs = saved[name]
+        a = ours()
         a.train(text, 256 + 80)
-        b.train(text, 256 + 80)
-        assert a.merges == b.merges and a.vocab == b.vocab
+        assert [list(p) for p in a.merges] == theirs["merges"]
         if name == "regex":
             a.register_special_tokens({"<|endoftext|>": 100257, "<|pad|>": 100258})
-            b.register_special_tokens({"<|endoftext|>": 100257, "<|pad|>": 100258})
         a.save(str(tmp_path / f"ours_{name}"))
-        b.save(str(tmp_path / f"ref_{name}"))
-        for ext in (".model", ".vocab"):
-            assert open(tmp_path / f"ours_{name}{ext}", "rb").read() == open(tmp_path / f"ref_{name}{ext}", "rb").read()
-        # and each side loads the other's file
+        for ext, key in ((".model", "model"), (".vocab", "vocab")):
+            assert open(tmp_path / f"ours_{name}{ext}", "rb").read() == theirs[key].encode("utf-8")
+        # and this package loads the reference's file
+        with open(tmp_path / f"ref_{name}.model", "wb") as f:
+            f.write(theirs["model"].encode("utf-8"))
         c = ours()
         c.load(str(tmp_path / f"ref_{name}.model"))
-        assert c.merges == b.merges and c.special_tokens == b.special_tokens and c.pattern == b.pattern
+        assert c.merges == a.merges and c.special_tokens == a.special_tokens and c.pattern == a.pattern
         probe = text[1000:3000]
-        assert c.encode(probe) == b.encode(probe) and c.decode(c.encode(probe)) == probe
+        assert c.encode(probe) == theirs["probe_ids"] and c.decode(c.encode(probe)) == probe
