@@ -8,7 +8,7 @@ import numpy as np
 import pytest
 
 import oracle
-from helpers import split_chunks
+from helpers import expand_weighted, hand_weighted, split_chunks, stands_for_bytes
 
 
 def chunks_of(data, offs):
@@ -116,3 +116,31 @@ def test_weighted_distinct_chunks_train_like_the_full_list(native):
         d2, o2, w, _ = native.dedup_chunks(data, offs)
         got_pairs, got_counts = weighted_train(chunks_of(d2, o2), [1 << int(k) for k in w], 80)
         assert got_pairs == exp_pairs and got_counts == exp_counts
+
+
+def test_weighted_oracle_with_hand_set_exponents_equals_the_written_out_list():
+    """oracle.train(..., weights=2^e) is the reference of the GPU tests on hand-weighted streams
+    (tests/test_gpu_weighted.py).  The test above pins it for the exponents a de-duplication emits; this one for
+    arbitrary ones: exponents 0..6 set by hand -- exponent 6 next to 0, one-byte chunks and empty chunks with
+    exponents, chunk starts at multiples of 256, 1024 and 4096 ids, a 2500-id run of one symbol -- against the plain
+    oracle on the list with every chunk written out 2^e times in place: pairs, counts, and the length of the
+    written-out list after every merge."""
+    data, offs, exps, edges = hand_weighted(900, 6, 6, seed=5, big_every=40)
+    lens = np.diff(np.append(offs, len(data)).astype(np.int64))
+    assert set(exps.tolist()) == set(range(7))
+    assert edges["singles"] and all(lens[i] == 1 and exps[i] == 6 and exps[i + 1] == 0 for i in edges["singles"])
+    assert edges["empties"] and all(lens[i] == 0 for i in edges["empties"])
+    assert any(exps[i] > 0 for i in edges["empties"])
+    assert sorted({m for m, _ in edges["aligned"]}) == [256, 1024, 4096]
+    assert all(int(offs[i]) % m == 0 and offs[i] > 0 and exps[i] == 6 and exps[i - 1] == 0 for m, i in edges["aligned"])
+    r = edges["run"]
+    assert data[int(offs[r]):int(offs[r]) + int(lens[r])] == b"z" * 2500 and int(offs[r]) % 1024 == 900 and exps[r] == 6
+    full, full_offs = expand_weighted(data, offs, exps)
+    assert len(full) == stands_for_bytes(offs, exps, len(data))
+    nm = 150
+    want = oracle.train(full, nm, full_offs, raise_on_empty=False)
+    got = oracle.train(data, nm, offs, raise_on_empty=False, weights=np.uint64(1) << exps.astype(np.uint64))
+    assert len(want[0]) == nm and any(a == b for a, b in want[0])
+    assert got[0] == want[0] and got[1] == want[1] and got[2] == want[2]
+    py_pairs, py_counts = weighted_train(chunks_of(data, offs), [1 << int(e) for e in exps], 25)
+    assert py_pairs == want[0][:25] and py_counts == want[1][:25]

@@ -6,7 +6,8 @@ import numpy as np
 import pytest
 
 import oracle
-from helpers import case_text, data_for, split_chunks, toy_rank_table
+from helpers import (CHAIN_DEFAULTS, CHAIN_OPTIONS, VARIANTS, case_text, data_for, reset_variant, set_variant,
+                     split_chunks, toy_rank_table)
 
 pytestmark = pytest.mark.gpu
 
@@ -115,47 +116,6 @@ def test_train_golden_cases(golden, engine, native):
             continue
         res = engine.train(nm)
         assert [list(p) for p in res["pairs"]] == case["merges"], case["name"]
-
-
-# engine variants: (mode, merge impl, slots, sparse, lean) -- slots 2 = the second slotted form (default);
-# sparse 2 = every a != b pass goes through the inverted index and the sparse kernel; lean 1 (default) =
-# lean iterations (k_lean.hip: three launches, table updated at the merge sites, a == b deferred to the
-# general path) once the host has seen a count <= lean_count, 2 = from the first merge on, 0 = never,
-# 3 = as 2 but every selection reads the whole row-maxima array (k_rowsel_lean; option lean_sum = 0)
-# instead of the previous table update's per-wave records (k_sel_lean, the default), 4 = as 2 but every
-# iteration selects (option lean_chain = 0: no tied pair is merged off an earlier selection's list), 5 = as 2
-# but a == b passes visit every slot and mark what they rewrite for an index rebuild (option aa_sparse = 0)
-VARIANTS = [(0, 0, 0, 1, 1), (1, 0, 1, 1, 1), (1, 0, 0, 1, 1), (1, 1, 0, 1, 1), (0, 1, 0, 1, 1), (1, 0, 2, 1, 1),
-            (1, 0, 2, 2, 1), (1, 0, 2, 0, 1), (1, 0, 2, 1, 0), (1, 0, 2, 2, 0), (1, 0, 2, 1, 2), (1, 0, 2, 2, 2),
-            (1, 0, 2, 2, 3), (1, 0, 2, 2, 4), (1, 0, 2, 2, 5), (1, 0, 2, 1, 7), (1, 0, 2, 2, 7), (1, 0, 2, 1, 8),
-            (1, 0, 2, 1, 9), (1, 0, 2, 2, 9), (1, 0, 2, 2, 10)]
-
-
-def set_variant(engine, mode, mimpl, slots, sparse, lean=1):
-    """lean: 0 never | 1 the default engine (chain steps, k_chain.hip, wherever lean iterations would run with the
-    index live) | 2 lean iterations forced onto every merge, no chain steps | 3, 4, 5 variants of 2 (selection from
-    the whole row-maxima array; no chained merges; a == b passes over every slot) | 7 = 2 with chain steps |
-    8 = 1 without chain steps (round 3's default engine) | 9 = 1 and 10 = 7 with the re-packing into 256-id slots (kernels of
-    namespace bpe_g1) forced onto streams of any size at the first index build (option small_slots = 2; the default does
-    it for streams of more than 16 Ki slots only)"""
-    engine.set_option("mode", mode)
-    engine.set_option("merge", mimpl)
-    engine.set_option("slots", slots)
-    engine.set_option("sparse", sparse)
-    engine.set_option("lean", 1 if lean in (1, 8, 9) else (2 if lean >= 2 else 0))
-    engine.set_option("chain", 1 if lean in (1, 7, 9, 10) else 0)
-    engine.set_option("small_slots", 2 if lean in (9, 10) else 1)
-    engine.set_option("lean_sum", 0 if lean == 3 else 1)
-    engine.set_option("lean_chain", 0 if lean == 4 else 1)
-    engine.set_option("aa_sparse", 0 if lean == 5 else 1)
-    # lean >= 2 forces the lean iterations onto every merge (coverage of their kernels and of the hand-back):
-    # no general-path stretches after clustered deferrals there
-    engine.set_option("lean_backoff", 0 if lean in (2, 3, 4, 5, 7, 10) else 1)
-
-
-def reset_variant(engine):
-    set_variant(engine, 1, 0, 2, 1, 1)
-    engine.set_option("depth", 8)
 
 
 @pytest.mark.parametrize("mode,mimpl,slots,sparse,lean", VARIANTS)
@@ -436,21 +396,6 @@ def test_repack_policy_vs_oracle(engine, native, kind, acc):
         engine.set_option("repack_acc", 200)
 
 
-CHAIN_OPTIONS = [
-    (("chain_kcap", 1),), (("chain_kcap", 4),), (("chain_kcap", 8),),   # batches of one, four, eight (default 15)
-    (("count_is_removed", 0),),                      # the ids a merge removes are counted, not taken from the pair's count
-    (("chain_prefetch", 0),),                        # no register prefetch of the next candidate slot
-    (("small_slots", 0),), (("small_slots", 2),),    # 1024-id slots throughout / 256-id slots from the first index build
-    (("small_slots", 2), ("chain_kcap", 2), ("pool_hint", 64)),
-    (("chain_scan", 1),), (("chain_scan", 63),), (("chain_scan", 255),),    # one / 63 / 255 scanning workgroups in a pool rebuild (default 127)
-    # a step as ONE launch (k_step: selection -> published batch -> merge pass -> grid barrier -> table update) instead of three
-    (("fuse_step", 1),), (("fuse_step", 1), ("chain_kcap", 4)), (("fuse_step", 1), ("count_is_removed", 0)),
-    (("fuse_step", 1), ("small_slots", 2)), (("fuse_step", 1), ("small_slots", 0)),
-    (("fuse_step", 1), ("lean_grid", 8)), (("fuse_step", 1), ("lean_grid", 70)),   # ... on a grid of 8 / 70 workgroups (its phases deal the work by the grid)
-    (("lean_grid", 8),),
-]
-
-
 @pytest.mark.parametrize("opts", CHAIN_OPTIONS)
 @pytest.mark.parametrize("kind", ["regex", "ties"])
 def test_chain_step_options_cross_check(engine, native, kind, opts):
@@ -468,8 +413,7 @@ def test_chain_step_options_cross_check(engine, native, kind, opts):
         offs = np.cumsum([0] + [len(c) for c in chunks[:-1]]).astype(np.uint64)
         nm = 400
     exp = oracle.train(data, nm, offs, raise_on_empty=False)
-    defaults = {"chain_kcap": 15, "count_is_removed": 1, "chain_prefetch": 1,
-                "small_slots": 1, "pool_hint": 0, "chain_scan": 127, "fuse_step": 0, "lean_grid": 256}
+    defaults = CHAIN_DEFAULTS
     set_variant(engine, 1, 0, 2, 2, 7)
     try:
         for k, v in opts:
