@@ -474,7 +474,8 @@ def _long_chunk_text(native, seed):
 def test_encode_batch_long_chunks_on_the_device(engine, native, cache, enc_long):
     """Chunks of more than 32 bytes (regex.py:92-109 on URLs, identifiers, whitespace runs): one wave per chunk with
     the chunk in LDS (k_enc_long, lengths up to 512, 4096 and 9216 bytes), the stream-wide rounds beyond that -- and
-    option enc_long = 0, every long chunk through the rounds -- all equal to oracle.encode."""
+    option enc_long = 0, every long chunk through the rounds -- all equal to oracle.encode.
+    (Random lengths; the exact seams -- 512 | 513, 4096 | 4097, 9216 | 9217 bytes -- are in test_gpu_encode_edges.py::test_tier_lattice.)"""
     pairs = _train_pairs(native, 300_000, 900, 61, "regex")
     text = _long_chunk_text(native, 62)
     data, offs = split_chunks(text)
