@@ -58,6 +58,8 @@ int bpe_set_stream(bpe_ctx *ctx, void *hip_stream);
  *   pass visits the slots the index names and keeps the index current), "enc_cache" (1), "enc_chain" (1),
  *   "sparse_ratio" (1), "tie_index" (1), "rep_min" (4), "rep_max" (8: log2 of delta replicas),
  *   "lds_delta" (1), "depth" (8: iterations the host runs ahead), "prof_stride" (64), "merge", "k1",
+ *   "chain_kcap" (1..31, default 31: most pairs a sparse chain step merges in one sweep; sharded steps: "dp_kcap",
+ *   1..15, default 8), "pool_hint" (0..128, 0 = chain_kcap: the pool is rebuilt when fewer untouched entries are left),
  *   "lb_tune", "scan_sup" (1024: the three-pass merge scans the tile summaries of streams of more tiles
  *   than this in three small launches instead of one workgroup). */
 int bpe_set_option(bpe_ctx *ctx, const char *name, int64_t value);

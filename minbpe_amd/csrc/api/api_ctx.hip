@@ -1212,6 +1212,7 @@ int launch_chain_step(bpe_ctx *c, uint32_t step, uint32_t zhi, bool use_index, b
     const DpComm *dp = c->dp_comm;
     uint32_t kcap = (uint32_t)(dense ? CH_KDENSE : std::min(CH_KSWEEP, c->chain_kcap));
     if (dp) kcap = std::min(kcap, (uint32_t)c->dp_kcap);
+    if (fused) kcap = std::min(kcap, (uint32_t)STEP_KCAP);  // (k_step's published line carries 15 pairs)
     const uint32_t hint_below = (uint32_t)(c->pool_hint > 0 ? c->pool_hint : (int)kcap);
     // (the deciding workgroup and the scanning ones wait for each other: all of them must be resident at once -- one
     // 1024-thread workgroup per CU at most, like lean_grid)

@@ -54,8 +54,8 @@ constexpr int ARGMAX_ROWS = 2048;  // rows attaining the max examined by k_selec
 constexpr uint32_t TIE_WINDOW0 = 0;  // positions k_select's block 0 searches alone on a tie (0: all blocks sweep together)
 constexpr int TIE_BLOCKS = 256;     // k_select blocks: block 0 decides, all of them sweep the stream on a tie
 constexpr int ROW_BLOCKS = 64;      // extra k_apply_delta blocks that recompute queued row maxima
-constexpr int DELTA_REPL = 256;    // replica blocks of the delta vectors (spreads hot atomics; a chain step's batch
-                                   // gives each of its pairs CH_RSTRIDE of them, k_chain.hip)
+constexpr int DELTA_REPL = 512;    // replica blocks of the delta vectors (spreads hot atomics; a chain step's batch
+                                   // gives each of its pairs CH_RSTRIDE of them, k_chain.hip: 32 pairs x 16)
 // Device-scope atomics execute at the memory channel that owns the address, ~11 ns apiece and ONE AT
 // A TIME per channel (measured: a pass whose atomics fall on few channels runs at a fraction of the
 // ~10 G atomics/s the whole chip sustains).  Replica r of the delta vectors starts at
@@ -73,17 +73,19 @@ __host__ __device__ inline size_t delta_rep_off(uint32_t r, uint32_t stride) {
 
 // Chain steps (k_chain.hip): the tied pairs at the maximum are kept as a LIST in first-occurrence order, and the
 // longest prefix of it whose pairs have a != b and share no token -- at most CH_KMAX of them -- is merged in ONE pass.
-constexpr int CH_KMAX = 16;                    // (array sizes)
-constexpr int CH_KSWEEP = 15;                  // most pairs one sweep merges: a word's pair number + 1 is a nibble (merge_chain_wave)
+constexpr int CH_KMAX = 32;                    // (array sizes)
+constexpr int CH_KSWEEP = 31;                  // most pairs one sweep merges: a word's pair number + 1 is a byte (merge_chain_wave); K < 32: one
+                                               // bit per pair in a word (k_pool.hip), 2 K removal-counter lanes in a wave
 constexpr int CH_RSTRIDE = 16;                 // replica blocks set aside per pair of a batch: all of them while its pairs have
 constexpr uint32_t CH_REP_COUNT = 16384;       // more sites than this (hot tokens queue ~11 ns per same-address atomic) ...
 constexpr int CH_REP = 4;                      // ... this many otherwise (the table update folds every replica it is told to)
-constexpr int CH_RMV = 16;                     // removal counters per pair of a batch (of the 256)
-constexpr int DP_KCAP_MAX = CH_KSWEEP;         // sharded chain steps: most pairs of a batch (option dp_kcap; the SUM payload grows with it: 2 K S words)
+constexpr int CH_RMV = 8;                      // removal counters per pair of a batch (of the 256)
+constexpr int DP_KCAP_MAX = 15;                // sharded chain steps: most pairs of a batch (option dp_kcap; the SUM payload grows with it: 2 K S words)
 constexpr int DP_KCAP_DEFAULT = 8;
 static_assert(CH_KMAX * CH_RSTRIDE <= DELTA_REPL, "a batch's delta vectors must fit the replica blocks");
 static_assert(CH_KMAX * CH_RMV <= 256, "removal counters of a batch");
-static_assert(CH_KSWEEP < 16 && CH_KSWEEP <= CH_KMAX, "pair number + 1 must fit a nibble");
+static_assert(CH_KSWEEP < 32 && CH_KSWEEP < CH_KMAX, "pair number + 1 must fit a byte, and one bit per pair a word");
+static_assert(DP_KCAP_MAX < 16 && DP_KCAP_MAX <= CH_KSWEEP, "sharded steps: the payload's tail holds 16 adj words");
 constexpr uint32_t CH_FULL = 0, CH_LIST = 1;   // DevState::sel_mode
 constexpr int DP_KEY_WORDS = TIE_CAP + 2;      // sharded chain steps: int64 words of the MIN all-reduce (k_pool_sel)
 

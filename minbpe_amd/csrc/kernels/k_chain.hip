@@ -155,7 +155,7 @@ __device__ __forceinline__ void merge_chain_wave(uint32_t *__restrict__ out, uin
     uint32_t tail[3];
 #pragma unroll
     for (int i = 0; i < 3; i++) tail[i] = at(TILE2 + i, 0u);
-    // ---- (4) r bits and, per site, WHICH pair (a nibble per word: pair index + 1) -------------
+    // ---- (4) r bits and, per site, WHICH pair (a byte per word: pair index + 1) ---------------
     uint32_t rb[MJ], jc[MJ], valid[MJ];
 #pragma unroll
     for (int j = 0; j < MJ; j++) {
@@ -167,7 +167,7 @@ __device__ __forceinline__ void merge_chain_wave(uint32_t *__restrict__ out, uin
     // latency): which pair's FIRST token is this word (K compares), then ONE compare of the next word with that
     // pair's second token, fetched from LDS by pair number (pb1[0] matches nothing: no pair).
     uint32_t s = 0;  // carry: my first word is the second word of a site that starts at the previous slot's last word
-    uint32_t ia[MJ];  // a nibble per word: the pair whose first token it is, + 1 (tokens are distinct: at most one)
+    uint32_t ia[MJ];  // a byte per word: the pair whose first token it is, + 1 (tokens are distinct: at most one)
 #pragma unroll
     for (int j = 0; j < MJ; j++) ia[j] = 0;
     uint32_t ip = 0;
@@ -178,12 +178,12 @@ __device__ __forceinline__ void merge_chain_wave(uint32_t *__restrict__ out, uin
         auto code = [&](uint32_t w) -> uint32_t {
             const uint32_t id = w & IDMASK;
             const uint32_t e = ph[(__umul24(id, hm) >> 8) & 255u];
-            return (e >> 8) == id ? (e & 15u) : 0u;
+            return (e >> 8) == id ? (e & 255u) : 0u;
         };
 #pragma unroll
         for (int j = 0; j < MJ; j++) {
 #pragma unroll
-            for (int k = 0; k < 4; k++) ia[j] |= code(x[j][k]) << (4 * k);
+            for (int k = 0; k < 4; k++) ia[j] |= code(x[j][k]) << (8 * k);
         }
         ip = code(prev1);
     } else {
@@ -192,7 +192,7 @@ __device__ __forceinline__ void merge_chain_wave(uint32_t *__restrict__ out, uin
 #pragma unroll
             for (int j = 0; j < MJ; j++) {
 #pragma unroll
-                for (int k = 0; k < 4; k++) ia[j] |= ((x[j][k] & IDMASK) == a) ? (p + 1u) << (4 * k) : 0u;
+                for (int k = 0; k < 4; k++) ia[j] |= ((x[j][k] & IDMASK) == a) ? (p + 1u) << (8 * k) : 0u;
             }
             ip = ((prev1 & IDMASK) == a) ? p + 1u : ip;
         }
@@ -204,10 +204,10 @@ __device__ __forceinline__ void merge_chain_wave(uint32_t *__restrict__ out, uin
 #pragma unroll
         for (int k = 0; k < 4; k++) {
             const uint32_t nxt = (k < 3) ? x[j][k + 1] : nxw;
-            const uint32_t i = (ia[j] >> (4 * k)) & 15u;
+            const uint32_t i = (ia[j] >> (8 * k)) & 255u;
             const uint32_t m = (uint32_t)((nxt & NWMASK) == pb1[i]);
             rb[j] |= m << k;
-            jc[j] |= (m ? i : 0u) << (4 * k);
+            jc[j] |= (m ? i : 0u) << (8 * k);
         }
     }
     s = (uint32_t)((prev1 != INVALID_WORD) & ((first & NWMASK) == pb1[ip]));
@@ -273,7 +273,7 @@ __device__ __forceinline__ void merge_chain_wave(uint32_t *__restrict__ out, uin
         for (int k = 0; k < 4; k++) {
             if ((kb[j] >> k) & 1u) {
                 const uint32_t w = x[j][k];
-                const uint32_t z = z0 + ((jc[j] >> (4 * k)) & 15u) - 1u;
+                const uint32_t z = z0 + ((jc[j] >> (8 * k)) & 255u) - 1u;
                 out[o++] = ((mb[j] >> k) & 1u) ? (z | (w & (FLAG | WMASK))) : w;
             }
         }
@@ -308,7 +308,7 @@ __device__ __forceinline__ void merge_chain_wave(uint32_t *__restrict__ out, uin
     // ---- (7) pair-table delta of my sites, as the sequential merges would charge it ------------
     // Which pair (if any) the two words before a site, and the two after it, are a site of: the codes of the
     // positions two to the left and two to the right -- computed above for every position, so a site only looks
-    // at its neighbours' nibbles (no search through the batch per site: the early passes have a site in nearly
+    // at its neighbours' bytes (no search through the batch per site: the early passes have a site in nearly
     // every group of words, and were bound by instruction issue while every site compared its neighbours with
     // every pair).  Positions -2 and -1 (the previous slot's last words) and 1024, 1025 come from the context words.
     const uint32_t vc = A.vcap & 0xFFFFFFu;
@@ -338,12 +338,12 @@ __device__ __forceinline__ void merge_chain_wave(uint32_t *__restrict__ out, uin
         W[4] = x[j][3];
         W[5] = lane_next(x[j][0], dn0);
         W[6] = lane_next(x[j][1], (j < MJ - 1) ? lane_first(x[(j + 1) % MJ][1]) : tail[1]);
-        // the codes of positions q0 - 2 .. q0 + 5, a nibble each
-        const uint32_t lo_fill = (j > 0) ? ((lane_last(jc[(j + MJ - 1) % MJ]) >> 8) & 0xFFu) : (cm2 | (cm1 << 4));
-        const uint32_t hi_fill = (j < MJ - 1) ? (lane_first(jc[(j + 1) % MJ]) & 0xFFu) : (ct0 | (ct1 << 4));
-        const uint32_t lo = (uint32_t)dpp_mov<0x138>((int)lo_fill, (int)((jc[j] >> 8) & 0xFFu));
-        const uint32_t hi = lane_next(jc[j] & 0xFFu, hi_fill);
-        const uint32_t win = lo | (jc[j] << 8) | (hi << 24);
+        // the codes of positions q0 - 2 .. q0 + 5, a byte each (64 bits: lo | my four | hi)
+        const uint32_t lo_fill = (j > 0) ? (lane_last(jc[(j + MJ - 1) % MJ]) >> 16) : (cm2 | (cm1 << 8));
+        const uint32_t hi_fill = (j < MJ - 1) ? (lane_first(jc[(j + 1) % MJ]) & 0xFFFFu) : (ct0 | (ct1 << 8));
+        const uint32_t lo = (uint32_t)dpp_mov<0x138>((int)lo_fill, (int)(jc[j] >> 16));
+        const uint32_t hi = lane_next(jc[j] & 0xFFFFu, hi_fill);
+        const unsigned long long win = (unsigned long long)lo | ((unsigned long long)jc[j] << 16) | ((unsigned long long)hi << 48);
         if (mb[j] == 0) continue;
         // A lane's four words hold at most TWO sites (no two sites of a batch overlap), and a sparse
         // pass has one or two sites in a whole slot: the lanes take their FIRST site together, then their second, instead
@@ -355,9 +355,9 @@ __device__ __forceinline__ void merge_chain_wave(uint32_t *__restrict__ out, uin
             const uint32_t k = (uint32_t)__ffs((int)todo) - 1u;
             todo &= todo - 1u;
             const int q = j * 256 + lane * 4 + (int)k;
-            const uint32_t wk = win >> (4u * k);
-            const uint32_t p = ((wk >> 8) & 15u) - 1u;
-            const int li = (int)(wk & 15u) - 1, ri = (int)((wk >> 16) & 15u) - 1;
+            const unsigned long long wk = win >> (8u * k);  // (positions q - 2 .. q + 2 in its low 40 bits)
+            const uint32_t p = ((uint32_t)(wk >> 16) & 255u) - 1u;
+            const int li = (int)((uint32_t)wk & 255u) - 1, ri = (int)((uint32_t)(wk >> 32) & 255u) - 1;
             const uint32_t Z = z0 + p;
             uint32_t *dl, *dr;  // SL, SR of pair p
             if (DENSE) {
@@ -407,24 +407,35 @@ __device__ __forceinline__ void merge_chain_wave(uint32_t *__restrict__ out, uin
     }
 }
 
-// The look-up table of a batch's first tokens (merge_chain_wave): wave 0 tries 64 multipliers at once, lane l its own,
-// and takes the first under which no two of the K tokens fall into the same of the 256 buckets (K <= 15: two in three
-// multipliers do); returns it to every thread (0: none found, or a batch too small to pay -- the pass compares).
-// s_ph: 256 words, s_hm: one word.  Every thread calls.
-// the multiplier itself (one wave; returns it to lane 0 .. 63 alike): 0 = none found, or a batch too small to pay
-__device__ __forceinline__ uint32_t chain_hash_find(const uint32_t *pa, uint32_t K) {
+// The look-up table of a batch's first tokens (merge_chain_wave): one wave looks for a multiplier m (odd, 129 .. 255) under
+// which no two of the K tokens fall into the same of the 256 buckets (K = 15: two in three multipliers do, K = 31: one in
+// six -- none of the 64 about once in 10^5 batches); returns it to every lane (0: none found, or a batch too small to pay
+// -- the pass compares).  Two multipliers per round, one per half of the wave, a token per lane: every lane writes its
+// number into its bucket of the half's table and reads the bucket back -- of two lanes in one bucket at least one reads
+// the other's number (no clearing: a lane only reads a bucket it has just written).  A round is two LDS accesses whatever
+// K is, and a small batch is done after one (K^2 / 2 compares per multiplier before: too many at K = 31).
+// tab: 512 words of LDS scratch.  All 64 lanes of the wave call.
+__device__ __forceinline__ uint32_t chain_hash_find(const uint32_t *pa, uint32_t K, uint32_t *tab) {
     if (K < 5) return 0u;
-    const uint32_t m = 129u + 2u * (uint32_t)lane_id();
-    bool ok = true;
-    for (uint32_t i = 1; i < K; i++) {
-        const uint32_t hi = (__umul24(pa[i], m) >> 8) & 255u;
-        for (uint32_t j = 0; j < i; j++) ok &= hi != ((__umul24(pa[j], m) >> 8) & 255u);
+    const uint32_t lane = (uint32_t)lane_id(), half = lane >> 5, l = lane & 31u;
+    const bool in = l < K;
+    const uint32_t a = in ? pa[l] : 0u;
+    volatile uint32_t *t = tab + half * 256u;
+    for (uint32_t m = 129u; m < 256u; m += 4u) {
+        const uint32_t h = (__umul24(a, m + 2u * half) >> 8) & 255u;
+        if (in) t[h] = l;
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+        __builtin_amdgcn_wave_barrier();
+        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+        const bool clash = in && t[h] != l;
+        const unsigned long long cb = __ballot(clash);
+        if ((uint32_t)cb == 0u) return m;
+        if ((uint32_t)(cb >> 32) == 0u) return m + 2u;
     }
-    const unsigned long long bal = __ballot(ok);
-    return bal ? 129u + 2u * (uint32_t)(__ffsll((long long)bal) - 1) : 0u;
+    return 0u;
 }
 // (pre_ok: the selection already found the multiplier, pre_hm -- k_pool.hip: pool_finish; DevState::bhm)
-__device__ __forceinline__ uint32_t chain_hash_build(uint32_t *s_ph, uint32_t *s_hm, const uint32_t *s_pa, uint32_t K,
+__device__ __forceinline__ uint32_t chain_hash_build(uint32_t *s_ph, uint32_t *s_hm, uint32_t *s_hs, const uint32_t *s_pa, uint32_t K,
                                                      bool pre_ok = false, uint32_t pre_hm = 0) {
     if (threadIdx.x < 256) s_ph[threadIdx.x] = 0xFFFFFFFFu;
     uint32_t hm = pre_hm;
@@ -432,7 +443,7 @@ __device__ __forceinline__ uint32_t chain_hash_build(uint32_t *s_ph, uint32_t *s
         if (threadIdx.x == 0) *s_hm = 0;
         __syncthreads();
         if (wave_id() == 0) {
-            const uint32_t f = chain_hash_find(s_pa, K);
+            const uint32_t f = chain_hash_find(s_pa, K, s_hs);
             if (lane_id() == 0) *s_hm = f;
         }
         __syncthreads();
@@ -455,6 +466,7 @@ struct MergeLds {
     uint32_t s_tot[2];
     uint32_t s_pa[CH_KMAX], s_pb[CH_KMAX], s_pb1[CH_KMAX + 1];
     uint32_t s_ph[256], s_hm;
+    uint32_t s_hs[512];  // (chain_hash_find's scratch)
 };
 // (s_pa / s_pb / s_pb1 are filled and a barrier has passed; every thread of the workgroup calls; THROUGH: k_step -- the
 // staged headers are committed by other workgroups of the same launch)
@@ -474,7 +486,7 @@ __device__ __forceinline__ void merge_chain_body(const AbArgs &A, const uint32_t
     auto &s_pa = L.s_pa;
     auto &s_pb = L.s_pb;
     auto &s_pb1 = L.s_pb1;
-    const uint32_t hm = chain_hash_build(L.s_ph, &L.s_hm, s_pa, K, pre_ok, pre_hm);
+    const uint32_t hm = chain_hash_build(L.s_ph, &L.s_hm, L.s_hs, s_pa, K, pre_ok, pre_hm);
     const uint32_t *s_ph = L.s_ph;
     // (have_st: the caller fetched the state words this pass needs in one round trip with the batch)
     const uint32_t Tl = min(A.T, have_st ? tlive_in : st->tlive);
@@ -555,26 +567,27 @@ __device__ __forceinline__ void merge_chain_body(const AbArgs &A, const uint32_t
 }
 // The words of DevState a chain step's merge pass / table update needs, fetched by 64 lanes at once (ONE round trip: the
 // fields used to be read where the code came to them -- status, then the batch, then tlive / gap: three dependent round
-// trips, ~4.5 us at the head of every launch): [p] = ba[p], [16 + p] = bb[p], [32 + p] = badj[p], then the scalars below.
-enum { SW_BK = 48, SW_BZ0, SW_BREP, SW_STATUS, SW_DEFER, SW_SEL_RAN, SW_TLIVE, SW_GAP, SW_BHM, SW_BHM_KEY, SW_ADJ, SW_N };
-static_assert(SW_N <= 64, "one wave fetches the state words");
+// trips, ~4.5 us at the head of every launch): [p] = ba[p], [SW_BB + p] = bb[p], [SW_BADJ + p] = badj[p], then the scalars below.
+enum { SW_BB = CH_KMAX, SW_BADJ = 2 * CH_KMAX, SW_BK = 3 * CH_KMAX, SW_BZ0, SW_BREP, SW_STATUS, SW_DEFER, SW_SEL_RAN, SW_TLIVE, SW_GAP, SW_BHM, SW_BHM_KEY, SW_ADJ, SW_N };
+constexpr int SW_WORDS = 128;  // (the LDS array)
+static_assert(SW_N <= SW_WORDS, "two waves fetch the state words");
 __device__ __forceinline__ void step_words_fetch(const DevState *st, uint32_t *s_w) {
     const uint32_t i = threadIdx.x;
     if (i < (uint32_t)SW_N) {
         const uint32_t *base = reinterpret_cast<const uint32_t *>(st);
         uint32_t off;
-        if (i < 16) off = (uint32_t)offsetof(DevState, ba) / 4 + i;
-        else if (i < 32) off = (uint32_t)offsetof(DevState, bb) / 4 + (i - 16);
-        else if (i < 48) off = (uint32_t)offsetof(DevState, badj) / 4 + (i - 32);
+        if (i < (uint32_t)SW_BB) off = (uint32_t)offsetof(DevState, ba) / 4 + i;
+        else if (i < (uint32_t)SW_BADJ) off = (uint32_t)offsetof(DevState, bb) / 4 + (i - (uint32_t)SW_BB);
+        else if (i < (uint32_t)SW_BK) off = (uint32_t)offsetof(DevState, badj) / 4 + (i - (uint32_t)SW_BADJ);
         else {
-            constexpr uint32_t o[SW_N - 48] = {
+            constexpr uint32_t o[SW_N - SW_BK] = {
                 (uint32_t)offsetof(DevState, bk) / 4,      (uint32_t)offsetof(DevState, bz0) / 4,     (uint32_t)offsetof(DevState, brep) / 4,
                 (uint32_t)offsetof(DevState, status) / 4,  (uint32_t)offsetof(DevState, defer) / 4,   (uint32_t)offsetof(DevState, sel_ran) / 4,
                 (uint32_t)offsetof(DevState, tlive) / 4,   (uint32_t)offsetof(DevState, gap) / 4,     (uint32_t)offsetof(DevState, bhm) / 4,
                 (uint32_t)offsetof(DevState, bhm_key) / 4, (uint32_t)offsetof(DevState, adj) / 4};
             off = o[0];
 #pragma unroll
-            for (int k = 1; k < SW_N - 48; k++) off = (i == 48u + (uint32_t)k) ? o[k] : off;
+            for (int k = 1; k < SW_N - SW_BK; k++) off = (i == (uint32_t)SW_BK + (uint32_t)k) ? o[k] : off;
         }
         s_w[i] = base[off];
     }
@@ -583,7 +596,7 @@ __device__ __forceinline__ void step_words_fetch(const DevState *st, uint32_t *s
 __global__ void __launch_bounds__(LEAN_MT)
 k_merge_chain(AbArgs A, const uint32_t *__restrict__ idx_dirty, uint32_t use_index, uint32_t *__restrict__ dbits) {
     __shared__ MergeLds L;
-    __shared__ uint32_t s_w[64];
+    __shared__ uint32_t s_w[SW_WORDS];
     DevState *st = A.st;
     step_words_fetch(st, s_w);
     // (the flagged rows were re-scanned by the selection launch before this one if that was a FULL one)
@@ -598,8 +611,8 @@ k_merge_chain(AbArgs A, const uint32_t *__restrict__ idx_dirty, uint32_t use_ind
     const uint32_t z0 = s_w[SW_BZ0], brep = s_w[SW_BREP];
     if (threadIdx.x < CH_KMAX) {
         L.s_pa[threadIdx.x] = threadIdx.x < K ? s_w[threadIdx.x] : 0xFFFFFFFFu;
-        L.s_pb[threadIdx.x] = threadIdx.x < K ? s_w[16 + threadIdx.x] : 0xFFFFFFFFu;
-        L.s_pb1[threadIdx.x + 1] = threadIdx.x < K ? s_w[16 + threadIdx.x] : 0xFFFFFFFFu;
+        L.s_pb[threadIdx.x] = threadIdx.x < K ? s_w[SW_BB + threadIdx.x] : 0xFFFFFFFFu;
+        L.s_pb1[threadIdx.x + 1] = threadIdx.x < K ? s_w[SW_BB + threadIdx.x] : 0xFFFFFFFFu;
         if (threadIdx.x == 0) L.s_pb1[0] = 0xFFFFFFFFu;  // (a masked word has its weight bits clear: never equal)
     }
     __syncthreads();
@@ -881,7 +894,7 @@ __device__ __forceinline__ void apply_chain_records(DevState *st, int par, IterR
                                                     const uint32_t status, const uint32_t defer, const uint32_t remote) {
     {
         // ids removed by the merge pass: CH_RMV counters per pair of the batch, one per 256-byte line (lane l: counters
-        // 4l .. 4l + 3, all of pair l / 4)
+        // 4l .. 4l + 3, all of pair l / 2)
         // (removed == nullptr: an unweighted stream -- a merge of a != b removes exactly as many ids as the pair counts, base.py:25-41:
         // nobody counted, the batch's counts are the answer)
         uint32_t v = 0;
@@ -893,22 +906,19 @@ __device__ __forceinline__ void apply_chain_records(DevState *st, int par, IterR
                 v += x;
             }
         }
-        static_assert(CH_RMV == 16, "lanes 4p .. 4p + 3 hold the removals of pair p");
+        static_assert(CH_RMV == 8 && 2 * CH_KMAX == 64, "lanes 2p, 2p + 1 hold the removals of pair p");
+        const uint32_t tot = wave_sum_u32(v);
         v += (uint32_t)__shfl_xor((int)v, 1);
-        v += (uint32_t)__shfl_xor((int)v, 2);
-        uint32_t rem[CH_KMAX];
-#pragma unroll
-        for (int p = 0; p < CH_KMAX; p++) rem[p] = (uint32_t)__shfl((int)v, 4 * p);
-        if (K == 1) {  // (a pair merged alone spreads over all the counters)
-            uint32_t tot = 0;
-#pragma unroll
-            for (int p = 0; p < CH_KMAX; p++) tot += rem[p];
-            rem[0] = tot;
+        // (to thread 0 through LDS: CH_KMAX registers indexed by its loop below would live in scratch)
+        __shared__ uint32_t rem[CH_KMAX];
+        if (!(threadIdx.x & 1u)) {
+            const uint32_t p = threadIdx.x >> 1;
+            // (K == 1: a pair merged alone spreads over all the counters)
+            rem[p] = removed ? ((K == 1 && p == 0) ? tot : v) : st->bcnt[p];
         }
-        if (!removed) {
-#pragma unroll
-            for (int p = 0; p < CH_KMAX; p++) rem[p] = st->bcnt[p];
-        }
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+        __builtin_amdgcn_wave_barrier();
+        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
         if (threadIdx.x == 0) {
             const unsigned long long n = st->n[par];
             unsigned long long nn = n;
@@ -985,7 +995,7 @@ k_apply_chain(uint32_t *__restrict__ mat, uint32_t stride, uint32_t *__restrict_
     // SL at folded[2p fS ..), SR at folded[(2p + 1) fS ..), its adj in ftail[p] -- instead of this rank's replica blocks
     // (sharded: ftail[16] = the number of ranks whose status was raised when they folded this step's delta -- a
     // failure inside any rank's merge pass stops every rank at this same merge)
-    __shared__ uint32_t s_w[64], s_pairs[CH_KMAX];
+    __shared__ uint32_t s_w[SW_WORDS], s_pairs[CH_KMAX];
     step_words_fetch(st, s_w);
     const uint32_t remote = (folded && ftail[16] != 0) ? 1u : 0u;
     const uint32_t status = s_w[SW_STATUS] ? s_w[SW_STATUS] : (remote ? ST_INTERNAL : 0u), defer = s_w[SW_DEFER];
@@ -993,11 +1003,11 @@ k_apply_chain(uint32_t *__restrict__ mat, uint32_t stride, uint32_t *__restrict_
     const bool noop = status || defer || K == 0;
     if (blockIdx.x < na) {
         if (noop) return;
-        if (threadIdx.x < CH_KMAX) s_pairs[threadIdx.x] = (s_w[threadIdx.x] << 16) | (s_w[16 + threadIdx.x] & 0xFFFFu);
-        if (threadIdx.x == 0 && K == 1) s_w[32] = s_w[SW_ADJ];  // (a batch of one: merge_ab_wave's adj word)
+        if (threadIdx.x < CH_KMAX) s_pairs[threadIdx.x] = (s_w[threadIdx.x] << 16) | (s_w[SW_BB + threadIdx.x] & 0xFFFFu);
+        if (threadIdx.x == 0 && K == 1) s_w[SW_BADJ] = s_w[SW_ADJ];  // (a batch of one: merge_ab_wave's adj word)
         __syncthreads();
         apply_chain_tokens<false>(blockIdx.x * 256u + threadIdx.x, mat, stride, delta, vcap, rowmax, dbits, sums, folded, fS,
-                                  ftail, K, z0, 0u, s_pairs, s_w + 32, s_w[SW_BREP]);
+                                  ftail, K, z0, 0u, s_pairs, s_w + SW_BADJ, s_w[SW_BREP]);
         return;
     }
     if (blockIdx.x == na && threadIdx.x < 64) apply_chain_records(st, par, rec, srec, step, removed, K, noop, status, defer, remote);
@@ -1113,10 +1123,10 @@ k_forced_sel(DevState *st, const int32_t *__restrict__ pairs, const uint32_t *__
     const uint32_t K = bb ? min(kcap, (uint32_t)__ffsll((long long)bb) - 1u) : kcap;
     const uint32_t c = lane < K ? mat[(size_t)a * stride + b] : 0u;
     const uint32_t cmax = wave_umax_dpp(c);
-    __shared__ uint32_t s_pa[CH_KMAX];
+    __shared__ uint32_t s_pa[CH_KMAX], s_hs[512];
     if (lane < CH_KMAX) s_pa[lane] = a;
     __syncthreads();
-    const uint32_t hm = chain_hash_find(s_pa, K);
+    const uint32_t hm = chain_hash_find(s_pa, K, s_hs);
     if (lane == 0) {
         st_agent(&st->adj, 0u);
         st->count = c;

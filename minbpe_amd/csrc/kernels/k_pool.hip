@@ -63,6 +63,7 @@ struct PoolScratch {
     uint32_t w[8];             // per wave: last / first level start
     uint32_t wtot[PL_CAP / 64];
     uint32_t fv, nl, k;
+    uint32_t bad;              // pool_finish: bit i = entry i cannot be in the batch
 };
 // entries ranked by count (descending; equal counts by pair): out[rank] = in[i].  n <= PL_GATHER, every thread
 // calls.  The order INSIDE a level is made later, from the keys, by a loop over the level alone.
@@ -169,7 +170,10 @@ __device__ __forceinline__ void pool_finish(DevState *st, PoolEnt *__restrict__ 
         X.rank[tid] = 0;
         X.dl[tid] = 0;
     }
-    if (tid == 0) *s_unt = 0;
+    if (tid == 0) {
+        *s_unt = 0;
+        X.bad = 0;
+    }
     __syncthreads();
     if (e < n) {
         const uint32_t lo = s_ls[e], hi = s_le[e];
@@ -197,25 +201,25 @@ __device__ __forceinline__ void pool_finish(DevState *st, PoolEnt *__restrict__ 
     }
     __syncthreads();
     // ---- the batch: the longest prefix with a != b, no chain, no first token twice, every level entered in a known order ----
-    if (tid < 64) {  // (nwalk <= CH_KSWEEP < 64: one wave)
-        uint32_t bad = 0;
-        if (tid < nwalk) {
-            const uint32_t x = a_xy[tid] >> 16, y = a_xy[tid] & 0xFFFFu;
-            bad = (x == y) | s_dirty[tid];
-#pragma unroll
-            for (uint32_t j = 0; j < (uint32_t)CH_KSWEEP - 1u; j++) {
-                if (j < tid) {
-                    const uint32_t xj = a_xy[j] >> 16, yj = a_xy[j] & 0xFFFFu;
-                    // (a SECOND token may be shared: sites of (a, b) and (c, b) never overlap and neither merge moves the
-                    // other's count -- only a pair that could chain onto a site of the batch, x a second token or y a first
-                    // one, stops the walk; first tokens stay distinct: the merge pass looks a pair up by its first token)
-                    bad |= (xj == x) | (xj == y) | (yj == x);
-                }
-            }
+    // (a thread per entry i and earlier entry j -- nwalk <= CH_KSWEEP < 32: 32 nwalk of them, one round of a 1024-thread
+    // selection; a wave that let entry i walk through every j < i took 30 dependent turns for a walk of 31)
+    for (uint32_t q2 = tid; q2 < 32u * nwalk; q2 += blockDim.x) {
+        const uint32_t i = q2 >> 5, j = q2 & 31u;
+        const uint32_t x = a_xy[i] >> 16, y = a_xy[i] & 0xFFFFu;
+        bool bad = false;
+        if (j == i) {
+            bad = (x == y) | (s_dirty[i] != 0);
+        } else if (j < i) {
+            const uint32_t xj = a_xy[j] >> 16, yj = a_xy[j] & 0xFFFFu;
+            // (a SECOND token may be shared: sites of (a, b) and (c, b) never overlap and neither merge moves the
+            // other's count -- only a pair that could chain onto a site of the batch, x a second token or y a first
+            // one, stops the walk; first tokens stay distinct: the merge pass looks a pair up by its first token)
+            bad = (xj == x) | (xj == y) | (yj == x);
         }
-        const unsigned long long bb = __ballot(bad != 0);
-        if (tid == 0) *s_k = bb ? min(nwalk, (uint32_t)__ffsll((long long)bb) - 1u) : nwalk;
+        if (bad) atomicOr(&X.bad, 1u << i);
     }
+    __syncthreads();
+    if (tid == 0) *s_k = X.bad ? min(nwalk, (uint32_t)__ffs((int)X.bad) - 1u) : nwalk;
     __syncthreads();
     const uint32_t K = *s_k;
     if (tid == 0) {
@@ -258,7 +262,7 @@ __device__ __forceinline__ void pool_finish(DevState *st, PoolEnt *__restrict__ 
         const uint32_t cmax = wave_umax_dpp(c);
         // the multiplier of the merge pass's first-token look-up table, found here once (chain_hash_find, k_chain.hip)
         // instead of by every workgroup of the pass; the key says which batch it belongs to
-        const uint32_t hm = chain_hash_find(reinterpret_cast<const uint32_t *>(X.rank), K);
+        const uint32_t hm = chain_hash_find(reinterpret_cast<const uint32_t *>(X.rank), K, X.rank + 256);
         if (tid == 0) {
             st->brep = cmax > CH_REP_COUNT ? (uint32_t)CH_RSTRIDE : (uint32_t)CH_REP;
             st->bhm = hm;
@@ -275,9 +279,8 @@ __device__ __forceinline__ void pool_finish(DevState *st, PoolEnt *__restrict__ 
         pool[tid - K] = e2;
         const uint32_t x = e2.xy >> 16, y = e2.xy & 0xFFFFu;
         bool touched = false;
-#pragma unroll
-        for (uint32_t p = 0; p < (uint32_t)CH_KSWEEP; p++)
-            if (p < K) touched |= ((a_xy[p] & 0xFFFFu) == x) | ((a_xy[p] >> 16) == y);
+#pragma unroll 4
+        for (uint32_t p = 0; p < K; p++) touched |= ((a_xy[p] & 0xFFFFu) == x) | ((a_xy[p] >> 16) == y);
         unt = !touched;
     }
     if (tid < PL_CAP) {
@@ -307,7 +310,7 @@ struct PoolLds {
     uint32_t s_rows[PL_ROWS], s_cnt[8], s_r16[16], s_wtot[PL_CAP / 64];
     uint32_t s_fail, s_n, s_theta, s_nrows, s_nl, s_reach, s_k, s_unt, s_x;
     PoolScratch X;
-    uint32_t s_sw[64];  // the words of st a selection needs (fetched at once)
+    uint32_t s_sw[3 * CH_KMAX];  // the words of st a selection needs (fetched at once)
 };
 // The selection: workgroup `blk` of `nblk` (0 decides, 1 .. nblk - 1 do a rebuild's row work); every thread calls.  Shared
 // by k_pool_sel (its own launch) and k_step (k_step.hip: the head of the step's one launch).
@@ -348,7 +351,7 @@ pool_sel_body(uint32_t *__restrict__ rowmax, uint32_t *__restrict__ mat, uint32_
     const uint32_t tid = threadIdx.x;
     // everything the selection needs from st, and its own pool entry, in ONE round trip (the fields used to be read where
     // the code came to them: three dependent round trips before the first table word was asked for)
-    enum { PW_STATUS = 32, PW_DEFER, PW_GAP, PW_ITER, PW_NM, PW_HINT, PW_THETA, PW_POOLN, PW_BK, PW_BZ0, PW_EPOCH_LO, PW_EPOCH_HI, PW_N };
+    enum { PW_BB = CH_KMAX, PW_STATUS = 2 * CH_KMAX, PW_DEFER, PW_GAP, PW_ITER, PW_NM, PW_HINT, PW_THETA, PW_POOLN, PW_BK, PW_BZ0, PW_EPOCH_LO, PW_EPOCH_HI, PW_N };
     PoolEnt my_ent;
     my_ent.xy = my_ent.c = 0;
     my_ent.key = 0;
@@ -356,17 +359,18 @@ pool_sel_body(uint32_t *__restrict__ rowmax, uint32_t *__restrict__ mat, uint32_
     if (tid < (uint32_t)PW_N) {
         const uint32_t *base = reinterpret_cast<const uint32_t *>(st);
         uint32_t off;
-        if (tid < 16) off = (uint32_t)offsetof(DevState, ba) / 4 + tid;
-        else if (tid < 32) off = (uint32_t)offsetof(DevState, bb) / 4 + (tid - 16);
+        if (tid < (uint32_t)PW_BB) off = (uint32_t)offsetof(DevState, ba) / 4 + tid;
+        else if (tid < (uint32_t)PW_STATUS) off = (uint32_t)offsetof(DevState, bb) / 4 + (tid - (uint32_t)PW_BB);
         else {
-            constexpr uint32_t o[PW_N - 32] = {
+            static_assert(PW_N <= 3 * CH_KMAX, "s_sw");
+            constexpr uint32_t o[PW_N - PW_STATUS] = {
                 (uint32_t)offsetof(DevState, status) / 4,     (uint32_t)offsetof(DevState, defer) / 4,      (uint32_t)offsetof(DevState, gap) / 4,
                 (uint32_t)offsetof(DevState, iter) / 4,       (uint32_t)offsetof(DevState, num_merges) / 4, (uint32_t)offsetof(DevState, pool_hint) / 4,
                 (uint32_t)offsetof(DevState, pool_theta) / 4, (uint32_t)offsetof(DevState, pool_n) / 4,     (uint32_t)offsetof(DevState, bk) / 4,
                 (uint32_t)offsetof(DevState, bz0) / 4,        (uint32_t)offsetof(DevState, pool_epoch) / 4, (uint32_t)offsetof(DevState, pool_epoch) / 4 + 1};
             off = o[0];
 #pragma unroll
-            for (int k = 1; k < PW_N - 32; k++) off = (tid == 32u + (uint32_t)k) ? o[k] : off;
+            for (int k = 1; k < PW_N - PW_STATUS; k++) off = (tid == (uint32_t)PW_STATUS + (uint32_t)k) ? o[k] : off;
         }
         L.s_sw[tid] = base[off];
     }
@@ -495,7 +499,7 @@ pool_sel_body(uint32_t *__restrict__ rowmax, uint32_t *__restrict__ mat, uint32_
         ekey = e.key;
         int32_t zx = -1, zy = -1;
         for (uint32_t p = 0; p < Kp; p++) {
-            if (s_sw[16 + p] == x) {
+            if (s_sw[PW_BB + p] == x) {
                 zx = (int32_t)(zp + p);
                 mxm |= 1u << p;
             }
@@ -755,23 +759,24 @@ pool_sel_body(uint32_t *__restrict__ rowmax, uint32_t *__restrict__ mat, uint32_
     pool_level_bounds(b_c, n, s_ls, s_le, X);
     pool_levels_dirty(b_key, n, s_ls, s_le, s_dirty, ksh, X);
     // does entry i < nwalk end a batch that reaches its level (a == b, or a token shared with anything above its level's
-    // end)?  Entry j looks at every such i (nwalk <= 15 broadcast reads) instead of entry i looking at every j.
+    // end)?  Entry j looks at every such i (nwalk <= CH_KSWEEP broadcast reads) instead of entry i looking at every j.
     if (tid < 64) s_clash[tid] = 0;
     if (tid == 0) {
         X.fv = 0xFFFFFFFFu;
         X.nl = 0;
     }
     __syncthreads();
-    if (tid < n) {
-        const uint32_t x = b_xy[tid] >> 16, y = b_xy[tid] & 0xFFFFu;
-#pragma unroll
-        for (uint32_t i = 0; i < (uint32_t)CH_KSWEEP; i++) {
-            if (i < nwalk) {
+    {
+        // (n <= PL_CAP = 256 entries, 1024 threads: thread t + 256 r takes the walk's entries r, r + 4, ... for entry t)
+        const uint32_t t = tid & (PL_CAP - 1u);
+        if (t < n) {
+            const uint32_t x = b_xy[t] >> 16, y = b_xy[t] & 0xFFFFu;
+            for (uint32_t i = tid / PL_CAP; i < nwalk; i += blockDim.x / PL_CAP) {
                 const uint32_t xi = b_xy[i] >> 16, yi = b_xy[i] & 0xFFFFu;
-                if (tid != i && tid < s_le[i] && ((xi == x) | (xi == y) | (yi == x))) s_clash[i] = 1;
+                if (t != i && t < s_le[i] && ((xi == x) | (xi == y) | (yi == x))) s_clash[i] = 1;
             }
+            if (tid < nwalk && x == y) s_clash[tid] = 1;
         }
-        if (tid < nwalk && x == y) s_clash[tid] = 1;
     }
     __syncthreads();
     if (tid < 64) {

@@ -38,8 +38,10 @@ namespace BPE_G {
 
 // the published line: [0] = K | brep << 8 | ran << 16 | noop << 17 | next hint << 18 | defer << 19 | mode << 21, [1] = 256 + merges done so far
 // (= the batch's first new id), [2 + p] = a_p << 16 | b_p, [17 + p] = the count of pair p
+// (the line carries 15 pairs: the host hands this launch a kcap of STEP_KCAP at most, whatever CH_KSWEEP is)
 constexpr uint32_t STEP_PUB_WORDS = 32;
-static_assert(2 + 2 * CH_KSWEEP == STEP_PUB_WORDS, "the line holds the pairs and their counts");
+constexpr int STEP_KCAP = 15;
+static_assert(2 + 2 * STEP_KCAP == STEP_PUB_WORDS && STEP_KCAP <= CH_KSWEEP, "the line holds the pairs and their counts");
 
 union StepLds {
     PoolLds p;
@@ -96,14 +98,14 @@ k_step(StepArgs S) {
             // (what thread 0 of this workgroup left in st: the same addresses read back through the same L2)
             const uint32_t status = st->status, defer = st->defer;
             const uint32_t noop = (status || defer) ? 1u : 0u;
-            const uint32_t K = noop ? 0u : min(st->bk, (uint32_t)CH_KSWEEP);
+            const uint32_t K = noop ? 0u : min(st->bk, (uint32_t)STEP_KCAP);
             uint32_t v = 0;
             if (tid == 0)
                 v = K | (st->brep << 8) | ((st->sel_ran ? 1u : 0u) << 16) | (noop << 17) | ((st->pool_hint_next ? 1u : 0u) << 18) |
                     ((defer & 3u) << 19) | ((st->sel_mode & 1u) << 21);
             else if (tid == 1) v = 256u + st->iter;
             else if (tid - 2 < K) v = ((uint32_t)st->ba[tid - 2] << 16) | ((uint32_t)st->bb[tid - 2] & 0xFFFFu);
-            else if (tid >= 2 + CH_KSWEEP && tid - (2 + CH_KSWEEP) < K) v = st->bcnt[tid - (2 + CH_KSWEEP)];
+            else if (tid >= 2 + STEP_KCAP && tid - (2 + STEP_KCAP) < K) v = st->bcnt[tid - (2 + STEP_KCAP)];
             s_b[tid] = v;
             granule_put(S.pub + tid, S.tag, v);
         }
@@ -180,7 +182,7 @@ k_step(StepArgs S) {
     if ((blockIdx.x == 0 || blockIdx.x == gridDim.x - 1) && wave_id() == 0) {
         const uint32_t lane = (uint32_t)lane_id();
         const uint32_t defer2 = (s_b[0] >> 19) & 3u, mode_used = (s_b[0] >> 21) & 1u, hint_next = (s_b[0] >> 18) & 1u;
-        // ids removed by the merge pass: CH_RMV counters per pair (lane l: counters 4l .. 4l + 3, all of pair l / 4), read at
+        // ids removed by the merge pass: CH_RMV counters per pair (lane l: counters 4l .. 4l + 3, all of pair l / 2), read at
         // agent scope (device atomics of this launch) -- or, an unweighted stream, nobody counted: a merge of a != b removes
         // exactly as many ids as the pair counts (base.py:25-41)
         uint32_t v = 0;
@@ -188,21 +190,16 @@ k_step(StepArgs S) {
 #pragma unroll
             for (int i = 0; i < 4; i++) v += ld_agent(&S.removed[(lane * 4 + i) * REMOVED_STRIDE]);
         }
-        static_assert(CH_RMV == 16, "lanes 4p .. 4p + 3 hold the removals of pair p");
+        static_assert(CH_RMV == 8, "lanes 2p, 2p + 1 hold the removals of pair p");
+        const uint32_t tot = wave_sum_u32(v);
         v += (uint32_t)__shfl_xor((int)v, 1);
-        v += (uint32_t)__shfl_xor((int)v, 2);
-        uint32_t rem[CH_KMAX];
+        uint32_t rem[STEP_KCAP + 1];
 #pragma unroll
-        for (int p = 0; p < CH_KMAX; p++) rem[p] = (uint32_t)__shfl((int)v, 4 * p);
-        if (K == 1) {  // (a pair merged alone spreads over all the counters)
-            uint32_t tot = 0;
-#pragma unroll
-            for (int p = 0; p < CH_KMAX; p++) tot += rem[p];
-            rem[0] = tot;
-        }
+        for (int p = 0; p < STEP_KCAP + 1; p++) rem[p] = (uint32_t)__shfl((int)v, 2 * p);
+        if (K == 1) rem[0] = tot;  // (a pair merged alone spreads over all the counters)
         if (!S.removed) {
 #pragma unroll
-            for (int p = 0; p < CH_KMAX; p++) rem[p] = p < CH_KSWEEP ? s_b[2 + CH_KSWEEP + p] : 0u;
+            for (int p = 0; p < STEP_KCAP + 1; p++) rem[p] = p < STEP_KCAP ? s_b[2 + STEP_KCAP + p] : 0u;
         }
         const uint32_t iter = z0 - 256u;
         unsigned long long nn = st->n[S.par];  // (an earlier launch's: workgroup 0 writes the OTHER parity below)
@@ -226,7 +223,7 @@ k_step(StepArgs S) {
                 unsigned long long m = st->n[S.par];
                 for (uint32_t p = 0; p < K; p++) {
                     m -= rem[p];
-                    iter_rec_put(S.rec + iter + p, (int32_t)(s_b[2 + p] >> 16), (int32_t)(s_b[2 + p] & 0xFFFFu), s_b[2 + CH_KSWEEP + p], ST_OK, m);
+                    iter_rec_put(S.rec + iter + p, (int32_t)(s_b[2 + p] >> 16), (int32_t)(s_b[2 + p] & 0xFFFFu), s_b[2 + STEP_KCAP + p], ST_OK, m);
                 }
                 __builtin_amdgcn_s_waitcnt(0);
                 for (uint32_t p = 0; p < K; p++) iter_rec_seal(S.rec + iter + p, (unsigned long long)(iter + p) + 1);
