@@ -61,7 +61,9 @@ int bpe_set_stream(bpe_ctx *ctx, void *hip_stream);
  *   "chain_kcap" (1..31, default 31: most pairs a sparse chain step merges in one sweep; sharded steps: "dp_kcap",
  *   1..15, default 8), "pool_hint" (0..128, 0 = chain_kcap: the pool is rebuilt when fewer untouched entries are left),
  *   "lb_tune", "scan_sup" (1024: the three-pass merge scans the tile summaries of streams of more tiles
- *   than this in three small launches instead of one workgroup). */
+ *   than this in three small launches instead of one workgroup);
+ *   bpe_decode_batch_resident's copy pass: "dec_copy" (1 staged through an LDS window, 16-byte stores | 0 one token
+ *   per lane, byte stores), "dec_window" (8192: bytes of that window), "dec_tile" (1024: tokens per workgroup tile). */
 int bpe_set_option(bpe_ctx *ctx, const char *name, int64_t value);
 
 /* ---- input ----------------------------------------------------------------- */
@@ -231,6 +233,28 @@ int bpe_decode_set_vocab(bpe_ctx *ctx, const uint8_t *vocab_bytes, const uint64_
 int bpe_decode_batch(bpe_ctx *ctx, const int32_t *ids, uint64_t n, uint64_t *n_bytes, uint64_t *bad_index);
 int bpe_decode_read(bpe_ctx *ctx, uint8_t *out, uint64_t cap, const uint64_t *doc_token_offsets,
                     uint64_t k, uint64_t *doc_byte_offsets_out);
+
+/* Ids outside [0, V_dense) that decode nevertheless: sparse_ids[j] (strictly ascending, each < 0 or >= V_dense)
+ * is table entry V_dense + j of the vocab given to bpe_decode_set_vocab, whose V must equal V_dense + n_sparse.
+ * Used by bpe_decode_batch_resident only; bpe_decode_set_vocab clears it (V_dense = V, no sparse ids). */
+int bpe_decode_set_sparse(bpe_ctx *ctx, const int32_t *sparse_ids, int32_t n_sparse, int32_t V_dense);
+
+/* bpe_decode_batch + bpe_decode_read with every large buffer ON THE DEVICE and owned by the caller:
+ *   d_ids                 n token ids, id_width = 4 (int32) or 8 (int64) bytes each, read in place, never written
+ *   d_doc_token_offsets   k token positions (each <= n; NULL with k = 0), validated on the device
+ *   d_out, out_cap        receives the bytes; NULL / 0 = only count
+ *   d_doc_byte_offsets    k entries: byte offset of each of those positions
+ *   *n_bytes              total bytes of the batch (set whenever the ids are valid, also on BPE_E_CAP)
+ *   *bad_index            first position whose id does not decode (~0 if none)
+ * An id that is neither in [0, V_dense) nor in the sparse list -- negative ids and 64-bit ids outside the int32
+ * range included -- fails with BPE_E_ARG and *bad_index; out_cap < total fails with BPE_E_CAP and writes nothing
+ * to d_out; a document position > n fails with BPE_E_ARG.  Never writes d_out[out_cap] or beyond, whatever the
+ * alignment of d_out.  Synchronises the ctx's stream before returning; keeps no pointer of the caller's.
+ * The ctx's decode scratch is shared with bpe_decode_batch: a result of that call not yet read is dropped. */
+int bpe_decode_batch_resident(bpe_ctx *ctx, const void *d_ids, int32_t id_width, uint64_t n,
+                              const uint64_t *d_doc_token_offsets, uint64_t k,
+                              uint8_t *d_out, uint64_t out_cap, uint64_t *d_doc_byte_offsets,
+                              uint64_t *n_bytes, uint64_t *bad_index);
 
 /* ---- measurement ------------------------------------------------------------ */
 #define BPE_PROF_WIDEN 0

@@ -95,6 +95,9 @@ _SIGS = {
     "bpe_decode_set_vocab": (C.c_int, [_p, _p, _p, _i32]),
     "bpe_decode_batch": (C.c_int, [_p, _p, _u64, C.POINTER(_u64), C.POINTER(_u64)]),
     "bpe_decode_read": (C.c_int, [_p, _p, _u64, _p, _u64, _p]),
+    "bpe_decode_set_sparse": (C.c_int, [_p, _p, _i32, _i32]),
+    "bpe_decode_batch_resident": (C.c_int, [_p, _p, _i32, _u64, _p, _u64, _p, _u64, _p, C.POINTER(_u64),
+                                            C.POINTER(_u64)]),
     "bpe_prof_reset": (C.c_int, [_p]),
     "bpe_prof_read": (C.c_int, [_p, _p, _p, _p]),
     "bpe_encode_uses_16bit": (C.c_int, [_p, C.c_int32]),
@@ -214,6 +217,14 @@ def dedup_chunks(data: bytes, offsets, threads: int = 0):
 
 class InvalidToken(Exception):
     """bpe_decode_batch met an id outside the vocab table; args[0] = its position."""
+
+
+class OutputTooSmall(ValueError):
+    """bpe_decode_batch_resident was given fewer bytes of room than the batch decodes to; needed = that number."""
+
+    def __init__(self, needed, msg):
+        super().__init__(msg)
+        self.needed = needed
 
 
 def _ptr(a):
@@ -526,6 +537,28 @@ class Engine:
         boff = np.zeros(len(doff), np.uint64)
         self._check(_lib.bpe_decode_read(self._h, _ptr(out), len(out), _ptr(doff), len(doff), _ptr(boff)))
         return out[:nb.value].tobytes(), boff
+
+    def decode_set_sparse(self, sparse_ids, v_dense: int):
+        """Ids outside [0, v_dense) that decode_batch_resident accepts: sparse_ids[j] (int32, strictly ascending) is
+        entry v_dense + j of the table given to decode_set_vocab, which resets the list."""
+        arr = np.ascontiguousarray(sparse_ids, dtype=np.int32)
+        self._check(_lib.bpe_decode_set_sparse(self._h, _ptr(arr) if len(arr) else None, len(arr), int(v_dense)))
+
+    def decode_batch_resident(self, d_ids: int, id_width: int, n: int, d_doc_off: int, k: int, d_out: int, out_cap: int,
+                              d_boff: int) -> int:
+        """decode_batch with the ids and the results in HBM: d_ids (n ids of id_width = 4 or 8 bytes), d_doc_off
+        (k uint64 token positions), d_out (room for out_cap bytes; 0 = only count), d_boff (k uint64) are device
+        addresses (e.g. torch tensor.data_ptr()).  Returns the number of bytes the batch decodes to.  An id that does
+        not decode raises InvalidToken(position); too little room raises OutputTooSmall."""
+        nb, bad = _u64(0), _u64(0)
+        rc = _lib.bpe_decode_batch_resident(self._h, C.c_void_p(d_ids), id_width, n, C.c_void_p(d_doc_off), k,
+                                            C.c_void_p(d_out), out_cap, C.c_void_p(d_boff), C.byref(nb), C.byref(bad))
+        if rc == BPE_E_ARG and bad.value != 0xFFFFFFFFFFFFFFFF:
+            raise InvalidToken(int(bad.value))
+        if rc == BPE_E_CAP:
+            raise OutputTooSmall(int(nb.value), (_lib.bpe_last_error(self._h) or b"").decode())
+        self._check(rc)
+        return int(nb.value)
 
     # -- measurement ----------------------------------------------------------------
     def prof_reset(self):

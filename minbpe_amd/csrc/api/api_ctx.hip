@@ -212,6 +212,13 @@ struct bpe_ctx {
     uint32_t dec_V = 0;
     bool dec_have_vocab = false, dec_have_result = false;
     uint64_t dec_n = 0, dec_total = 0;
+    // bpe_decode_batch_resident: ids outside [0, dec_V_dense) that decode (sorted; entry j = table index dec_V_dense + j)
+    int32_t *d_dec_sparse = nullptr;
+    uint64_t cap_dec_sparse = 0;
+    uint32_t dec_V_dense = 0, dec_n_sparse = 0;
+    int dec_copy = 1;        // option "dec_copy": 1 = k_decode_copy_staged (LDS window, 16-byte stores) | 0 = k_decode_copy (one token per lane)
+    int dec_window = 8192;   // option "dec_window": bytes of the staged copy's LDS window
+    int dec_tile = 1024;     // option "dec_tile": tokens per workgroup tile of the staged copy
 
     int mode = 1;     // 0 recount | 1 delta
     int profile = 0;  // 0 off | 1 hipEvents around the merge pass | 2 around every kernel class

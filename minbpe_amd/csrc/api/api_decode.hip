@@ -29,7 +29,39 @@ extern "C" int bpe_decode_set_vocab(bpe_ctx *c, const uint8_t *vocab_bytes, cons
                              hipMemcpyHostToDevice, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));  // caller may free its buffers on return
     c->dec_V = (uint32_t)V;
+    c->dec_V_dense = (uint32_t)V;  // (no sparse ids until bpe_decode_set_sparse)
+    c->dec_n_sparse = 0;
     c->dec_have_vocab = true;
+    return BPE_OK;
+}
+
+extern "C" int bpe_decode_set_sparse(bpe_ctx *c, const int32_t *sparse_ids, int32_t n_sparse, int32_t V_dense) {
+    if (!c || n_sparse < 0 || V_dense < 0 || (!sparse_ids && n_sparse)) return fail(c, BPE_E_ARG, "bad arguments");
+    if (!c->dec_have_vocab) return fail(c, BPE_E_STATE, "bpe_decode_set_vocab first");
+    if ((uint64_t)V_dense + (uint64_t)n_sparse != c->dec_V)
+        return fail(c, BPE_E_ARG, "V_dense + n_sparse = %lld, the vocab table has %u entries",
+                    (long long)V_dense + n_sparse, c->dec_V);
+    for (int32_t j = 0; j < n_sparse; j++) {
+        if (sparse_ids[j] >= 0 && sparse_ids[j] < V_dense)
+            return fail(c, BPE_E_ARG, "sparse_ids[%d] = %d lies inside [0, V_dense)", j, sparse_ids[j]);
+        if (j && sparse_ids[j] <= sparse_ids[j - 1])
+            return fail(c, BPE_E_ARG, "sparse_ids must ascend strictly (entry %d)", j);
+    }
+    HIPCHK(c, hipSetDevice(c->device));
+    if ((uint64_t)n_sparse > c->cap_dec_sparse) {
+        c->dec_V_dense = c->dec_V;  // (nothing half set if the allocation fails)
+        c->dec_n_sparse = 0;
+        c->cap_dec_sparse = 0;
+        TRY(dev_realloc(c, c->d_dec_sparse, (size_t)n_sparse));
+        c->cap_dec_sparse = (uint64_t)n_sparse;
+    }
+    if (n_sparse) {
+        HIPCHK(c, hipMemcpyAsync(c->d_dec_sparse, sparse_ids, (size_t)n_sparse * sizeof(int32_t), hipMemcpyHostToDevice,
+                                 c->stream));
+        HIPCHK(c, hipStreamSynchronize(c->stream));  // caller may free its buffer on return
+    }
+    c->dec_V_dense = (uint32_t)V_dense;
+    c->dec_n_sparse = (uint32_t)n_sparse;
     return BPE_OK;
 }
 
@@ -117,12 +149,106 @@ extern "C" int bpe_decode_read(bpe_ctx *c, uint8_t *out, uint64_t cap, const uin
             HIPCHK(c, hipMemcpyAsync(t_idx.p, doc_token_offsets, k * 8, hipMemcpyHostToDevice, c->stream));
             hipLaunchKernelGGL(k_decode_doc_offsets, dim3((unsigned)((k + 255) / 256)), dim3(256), 0, c->stream,
                                c->d_dec_off, c->dec_n, (unsigned long long)c->dec_total, t_idx.as<unsigned long long>(), k,
-                               t_dst.as<unsigned long long>());
+                               t_dst.as<unsigned long long>(), (unsigned long long *)nullptr);
             LAUNCHCHK(c, "k_decode_doc_offsets");
             HIPCHK(c, hipMemcpyAsync(doc_byte_offsets_out, t_dst.p, k * 8, hipMemcpyDeviceToHost, c->stream));
             HIPCHK(c, hipStreamSynchronize(c->stream));
         }
     }
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return BPE_OK;
+}
+
+// Resident form: ids, document positions, bytes and byte offsets are the caller's device buffers; lengths, resolved table
+// indices, offsets and block sums are the ctx's decode scratch (shared with bpe_decode_batch, whose pending result this
+// call therefore drops).  Host <-> device: the counters {bad position, total, bad document entry}, nothing else.
+extern "C" int bpe_decode_batch_resident(bpe_ctx *c, const void *d_ids, int32_t id_width, uint64_t n,
+                                         const uint64_t *d_doc_token_offsets, uint64_t k, uint8_t *d_out,
+                                         uint64_t out_cap, uint64_t *d_doc_byte_offsets, uint64_t *n_bytes,
+                                         uint64_t *bad_index) {
+    if (!c || (!d_ids && n)) return fail(c, BPE_E_ARG, "bad arguments");
+    if (id_width != 4 && id_width != 8) return fail(c, BPE_E_ARG, "id_width must be 4 (int32) or 8 (int64)");
+    if (k && (!d_doc_token_offsets || !d_doc_byte_offsets)) return fail(c, BPE_E_ARG, "offset arrays are NULL");
+    if (!c->dec_have_vocab) return fail(c, BPE_E_STATE, "bpe_decode_set_vocab first");
+    if (n_bytes) *n_bytes = 0;
+    if (bad_index) *bad_index = ~0ull;
+    HIPCHK(c, hipSetDevice(c->device));
+    c->dec_have_result = false;
+    const uint64_t nb = (n + SCAN_TILE - 1) / SCAN_TILE;
+    if (n > c->cap_dec_n) {
+        TRY(dev_realloc(c, c->d_dec_ids, (size_t)n));
+        TRY(dev_realloc(c, c->d_dec_len, (size_t)n));
+        TRY(dev_realloc(c, c->d_dec_off, (size_t)n + 1));
+        TRY(dev_realloc(c, c->d_dec_bsum, (size_t)nb + 1));
+        c->cap_dec_n = n;
+    }
+    unsigned long long *d_bad = c->d_scratch, *d_total = c->d_scratch + 1, *d_docbad = c->d_scratch + 2;
+    uint32_t *d_tidx = (uint32_t *)c->d_dec_ids;
+    HIPCHK(c, hipMemsetAsync(d_bad, 0xFF, 3 * sizeof(unsigned long long), c->stream));
+    if (n == 0) {
+        HIPCHK(c, hipMemsetAsync(d_total, 0, sizeof(unsigned long long), c->stream));
+    } else {
+        TRY(prof_begin(c, BPE_PROF_DECODE, (uint64_t)id_width * n));
+        const dim3 grid(grid_for(n, 256, c->num_cus * 8));
+        if (id_width == 4)
+            hipLaunchKernelGGL(k_decode_res_len<int32_t>, grid, dim3(256), 0, c->stream, (const int32_t *)d_ids, n,
+                               c->d_dec_voff, c->dec_V_dense, c->d_dec_sparse, c->dec_n_sparse, d_tidx, c->d_dec_len, d_bad);
+        else
+            hipLaunchKernelGGL(k_decode_res_len<int64_t>, grid, dim3(256), 0, c->stream, (const int64_t *)d_ids, n,
+                               c->d_dec_voff, c->dec_V_dense, c->d_dec_sparse, c->dec_n_sparse, d_tidx, c->d_dec_len, d_bad);
+        LAUNCHCHK(c, "k_decode_res_len");
+        hipLaunchKernelGGL(k_scan_blocksum, dim3((unsigned)nb), dim3(256), 0, c->stream, c->d_dec_len, n, c->d_dec_bsum);
+        hipLaunchKernelGGL(k_scan_top, dim3(1), dim3(1024), 0, c->stream, c->d_dec_bsum, nb, d_total);
+        hipLaunchKernelGGL(k_scan_apply, dim3((unsigned)nb), dim3(256), 0, c->stream, c->d_dec_len, n, c->d_dec_bsum,
+                           c->d_dec_off);
+        LAUNCHCHK(c, "k_scan_*");
+        TRY(prof_end(c));
+    }
+    unsigned long long hb[3] = {0, 0, 0};  // {first bad position, total bytes, first bad document entry}
+    HIPCHK(c, hipMemcpyAsync(hb, c->d_scratch, 2 * sizeof(unsigned long long), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    if (hb[0] != ~0ull) {
+        if (bad_index) *bad_index = hb[0];
+        TRY(prof_drain(c));
+        return fail(c, BPE_E_ARG, "invalid token id at position %llu", hb[0]);
+    }
+    const uint64_t total = hb[1];
+    if (n_bytes) *n_bytes = total;
+    if (k) {
+        hipLaunchKernelGGL(k_decode_doc_offsets, dim3((unsigned)((k + 255) / 256)), dim3(256), 0, c->stream, c->d_dec_off, n,
+                           (unsigned long long)total, (const unsigned long long *)d_doc_token_offsets, k,
+                           (unsigned long long *)d_doc_byte_offsets, d_docbad);
+        LAUNCHCHK(c, "k_decode_doc_offsets");
+        HIPCHK(c, hipMemcpyAsync(hb + 2, d_docbad, sizeof(unsigned long long), hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+        if (hb[2] != ~0ull) {
+            TRY(prof_drain(c));
+            return fail(c, BPE_E_ARG, "doc_token_offsets[%llu] is past the last token", hb[2]);
+        }
+    }
+    if (!d_out || out_cap == 0 || total == 0) {  // only count (or nothing to write)
+        TRY(prof_drain(c));
+        return BPE_OK;
+    }
+    if (out_cap < total) {
+        TRY(prof_drain(c));
+        return fail(c, BPE_E_CAP, "need %llu bytes", (unsigned long long)total);
+    }
+    TRY(prof_begin(c, BPE_PROF_DECODE, total));
+    if (c->dec_copy) {
+        const uint64_t ntiles = (n + (uint64_t)c->dec_tile - 1) / (uint64_t)c->dec_tile;
+        const unsigned grid = (unsigned)std::min<uint64_t>(ntiles, (uint64_t)c->num_cus * 64);
+        hipLaunchKernelGGL(k_decode_copy_staged, dim3(grid), dim3(256), (size_t)c->dec_window, c->stream, d_tidx, n,
+                           c->d_dec_voff, c->d_dec_blob, c->d_dec_off, (unsigned long long)total, d_out,
+                           (uint32_t)c->dec_tile, (uint32_t)c->dec_window);
+        LAUNCHCHK(c, "k_decode_copy_staged");
+    } else {  // one token per lane over the resolved indices (every one is a table index: the check passes)
+        hipLaunchKernelGGL(k_decode_copy, dim3(grid_for(n, 256, c->num_cus * 8)), dim3(256), 0, c->stream,
+                           (const int32_t *)d_tidx, n, c->d_dec_voff, c->dec_V, c->d_dec_blob, c->d_dec_off, d_out);
+        LAUNCHCHK(c, "k_decode_copy");
+    }
+    TRY(prof_end(c));
+    TRY(prof_drain(c));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     return BPE_OK;
 }

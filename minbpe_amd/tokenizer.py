@@ -185,15 +185,12 @@ class Tokenizer:
             while V in vocab:
                 V += 1
             table = [vocab[i] for i in range(V)]
+            outside = {idx: tok.encode("utf-8") for idx, tok in extra.items() if idx not in vocab}
+            outside.update((idx, tok) for idx, tok in vocab.items() if not 0 <= idx < V)
             sparse = {}
-            for idx, tok in vocab.items():
-                if not 0 <= idx < V:
-                    sparse[idx] = len(table)
-                    table.append(tok)
-            for idx, tok in extra.items():
-                if idx not in vocab:
-                    sparse[idx] = len(table)
-                    table.append(tok.encode("utf-8"))
+            for idx in sorted(outside):  # ascending ids: the order bpe_decode_set_sparse takes them in
+                sparse[idx] = len(table)
+                table.append(outside[idx])
             offs = np.zeros(len(table) + 1, dtype=np.uint64)
             np.cumsum(np.fromiter((len(t) for t in table), dtype=np.uint64, count=len(table)), out=offs[1:])
             self._dt_cache = (key, b"".join(table), offs, V, sparse)
@@ -220,13 +217,85 @@ class Tokenizer:
                     raise self._invalid_token(int(arr[p]))
                 arr[p] = j
         eng = engine()
-        if getattr(eng, "_decode_owner", None) is not blob:  # the table stays resident per engine
+        # the table stays resident per engine: _decode_owner = (the blob uploaded, its sparse list is uploaded too)
+        if getattr(eng, "_decode_owner", (None, False))[0] is not blob:
             eng.decode_set_vocab(blob, offs)
-            eng._decode_owner = blob
+            eng._decode_owner = (blob, False)
         res = eng.decode_batch(arr.astype(np.int32), doc_offsets)
         if doc_offsets is None:
             return self._finish_bytes(res)
         return self._finish_bytes(res[0]), res[1]
+
+    def _resident_blob(self, blob):
+        """the table bytes as the device-resident decode emits them (_finish_bytes applied to the table)"""
+        return blob
+
+    def _decode_table_resident(self):
+        """_decode_table() for decode_batch_resident: (blob, offsets, V_dense, sparse_ids) -- ids 0..V_dense-1 are
+        table indices as they are, sparse_ids (int32, strictly ascending) are the other known ids, the j-th being table
+        entry V_dense + j; the blob already carries what _finish_bytes does to the output (a per-byte map of the
+        output is the same map of the table: every output byte is a copy of a table byte)."""
+        blob, offs, V, sparse = self._decode_table()
+        cached = getattr(self, "_dtr_cache", None)
+        if cached is None or cached[0] is not blob:
+            ids = sorted(sparse, key=sparse.get)  # table order (= ascending: _decode_table)
+            if any(not -2**31 <= i < 2**31 for i in ids):
+                raise ValueError("decode_batch_resident needs every special token id to fit int32")
+            self._dtr_cache = (blob, self._resident_blob(blob), np.array(ids, dtype=np.int32))
+        return self._dtr_cache[1], offs, V, self._dtr_cache[2]
+
+    def decode_batch_resident(self, ids, doc_offsets=None, out=None):
+        """decode_batch() for token ids that live in HBM, with the bytes left in HBM: `ids` is a 1-D contiguous int32
+        or int64 torch tensor on the GPU, the result a uint8 tensor there (with doc_offsets -- a tensor on the GPU or
+        anything np.asarray takes -- also the int64 byte offset of each position).  Nothing but counters crosses PCIe;
+        special tokens and 64-bit ids are resolved on the device.  out: a uint8 tensor on the same GPU to decode
+        into (the view out[:total] is returned; ValueError if it is too small); without it the batch is measured by
+        a count-only call first.  Unknown ids raise what decode() raises, for the first such id."""
+        import torch
+        if not isinstance(ids, torch.Tensor) or not ids.is_cuda or ids.dim() != 1 or not ids.is_contiguous() \
+                or ids.dtype not in (torch.int32, torch.int64):
+            raise TypeError("ids must be a 1-D contiguous int32 or int64 torch tensor on the GPU")
+        dev = ids.device
+        if out is not None and (not isinstance(out, torch.Tensor) or out.device != dev or out.dtype != torch.uint8
+                                or out.dim() != 1 or not out.is_contiguous()):
+            raise TypeError("out must be a 1-D contiguous uint8 torch tensor on the device of ids")
+        blob, offs, V, sparse_ids = self._decode_table_resident()
+        eng = engine(dev.index)
+        owner = getattr(eng, "_decode_owner", (None, False))
+        if owner[0] is not blob or not owner[1]:
+            eng.decode_set_vocab(blob, offs)
+            eng.decode_set_sparse(sparse_ids, V)
+            eng._decode_owner = (blob, True)
+        n, width = ids.numel(), ids.element_size()
+        doff, boff, k = None, None, 0
+        if doc_offsets is not None:
+            if isinstance(doc_offsets, torch.Tensor):
+                if doc_offsets.device != dev or doc_offsets.dtype not in (torch.int32, torch.int64):
+                    raise TypeError("doc_offsets must be an integer tensor on the device of ids")
+                doff = doc_offsets.to(torch.int64).contiguous().reshape(-1)
+            else:
+                doff = torch.from_numpy(np.ascontiguousarray(doc_offsets, dtype=np.int64).reshape(-1)).to(dev)
+            k = doff.numel()
+            boff = torch.empty(k, dtype=torch.int64, device=dev)
+        torch.cuda.current_stream(dev).synchronize()  # the caller's pending writes to ids (and uploads above) are done
+
+        def call(dst, with_docs):
+            try:
+                return eng.decode_batch_resident(ids.data_ptr(), width, n, doff.data_ptr() if with_docs else 0,
+                                                 k if with_docs else 0, 0 if dst is None else dst.data_ptr(),
+                                                 0 if dst is None else dst.numel(), boff.data_ptr() if with_docs else 0)
+            except _native.InvalidToken as e:
+                raise self._invalid_token(int(ids[e.args[0]].item())) from None
+            except _native.OutputTooSmall as e:
+                raise ValueError(f"out holds {dst.numel()} bytes, the batch decodes to {e.needed}") from None
+
+        if out is None:
+            out = torch.empty(call(None, False), dtype=torch.uint8, device=dev)
+        elif out.numel() == 0 and call(None, False):  # (no room at all is a count-only call to the library)
+            raise ValueError("out holds 0 bytes")
+        total = call(out, k > 0)
+        res = out[:total]
+        return res if doc_offsets is None else (res, boff)
 
     # -- persistence (file formats of base.py:97-165, byte for byte) -----------------
     def save(self, file_prefix):
@@ -483,6 +552,9 @@ class GPT4Tokenizer(RegexTokenizer):
 
     def _finish_bytes(self, raw):
         return raw.translate(self._unshuffle_lut)
+
+    def _resident_blob(self, blob):
+        return blob.translate(self._unshuffle_lut)
 
     def train(self, text, vocab_size, verbose=False):
         raise NotImplementedError
