@@ -636,26 +636,55 @@ def _space_chunks(text: bytes):
     return [c for c in re.findall(rb" ?[^ ]+| +", text) if c]
 
 
-def _lockstep(native, chunks, nm, world, slots=2, dedup=False, sparse=1):
-    """Drive `world` ctxs through the dist.py protocol in lock-step; reductions done by hand."""
+def _rank_inputs(chunks, world, shards, rank_ids, nranks, rank_opts, weights):
+    """what the two emulated-rank drivers below share: (per-rank chunk lists, rank numbers, claimed world size, per-rank
+    option lists, per-rank weight exponents).  Default: `chunks` cut into `world` equal parts, ranks 0 .. world - 1."""
+    from minbpe_amd.dist import shard_chunks
+    if shards is None:
+        shards = [chunks[slice(*shard_chunks(len(chunks), r, world))] for r in range(world)]
+    world = len(shards)
+    rank_ids = list(range(world)) if rank_ids is None else list(rank_ids)
+    nranks = world if nranks is None else nranks
+    assert len(rank_ids) == world and sorted(set(rank_ids)) == rank_ids and rank_ids[-1] < nranks  # (rank order = shard order)
+    rank_opts = [()] * world if rank_opts is None else rank_opts
+    weights = [None] * world if weights is None else weights
+    assert len(rank_opts) == world and len(weights) == world
+    return shards, rank_ids, nranks, rank_opts, weights
+
+
+def _load_shard(native, eng, mine, dedup, wexp):
+    data = b"".join(mine)
+    offs = np.cumsum([0] + [len(c) for c in mine[:-1]]).astype(np.uint64) if mine else None
+    if dedup and mine:  # every rank de-duplicates its own shard
+        d2, o2, w, _ = native.dedup_chunks(data, offs)
+        eng.load_bytes(d2, o2, w)
+    elif wexp is not None and mine:
+        eng.load_bytes(data, offs, wexp)
+    else:
+        eng.load_bytes(data, offs)
+
+
+def _lockstep(native, chunks, nm, world, slots=2, dedup=False, sparse=1, *, shards=None, rank_ids=None, nranks=None,
+              rank_opts=None, weights=None, inspect=None):
+    """Drive `world` ctxs through the dist.py protocol in lock-step; reductions done by hand.
+    shards: per-rank chunk lists (a rank's may be empty) in place of equal parts of `chunks`; rank_ids / nranks: the rank
+    number each emulated rank passes and the world size it claims (the reductions run over the emulated ranks: an
+    absent rank would contribute neutral values); rank_opts: per-rank option lists, set after slots and sparse;
+    weights: per-rank weight exponents (load_bytes(data, offs, e)); inspect(r, engine) is called after the run, before
+    the engine closes -- with it the return value is (pairs, counts, lens, [what inspect returned], final status)."""
     import torch
-    from minbpe_amd.dist import GpuShard, shard_chunks
+    from minbpe_amd.dist import GpuShard
+    parts, rank_ids, nranks, rank_opts, weights = _rank_inputs(chunks, world, shards, rank_ids, nranks, rank_opts, weights)
     shards = []
-    for r in range(world):
-        lo, hi = shard_chunks(len(chunks), r, world)
-        mine = chunks[lo:hi]
+    for r, mine in enumerate(parts):
         eng = native.Engine(0)
         eng.set_option("slots", slots)
         eng.set_option("sparse", sparse)
-        data = b"".join(mine)
-        offs = np.cumsum([0] + [len(c) for c in mine[:-1]]).astype(np.uint64) if mine else None
-        if dedup:  # every rank de-duplicates its own shard
-            d2, o2, w, _ = native.dedup_chunks(data, offs)
-            eng.load_bytes(d2, o2, w)
-        else:
-            eng.load_bytes(data, offs)
+        for k, v in rank_opts[r]:
+            eng.set_option(k, v)
+        _load_shard(native, eng, mine, dedup, weights[r])
         sh = GpuShard(eng, 0)
-        sh.begin(nm, r, world)
+        sh.begin(nm, rank_ids[r], nranks)
         shards.append(sh)
 
     def allreduce(name, op):
@@ -677,18 +706,25 @@ def _lockstep(native, chunks, nm, world, slots=2, dedup=False, sparse=1):
         for sh in shards:
             sh.apply(i)
     pairs, counts, lens = [], [], []
+    status = 0
     for i in range(nm):
         recs = [sh.poll(i) for sh in shards]
         if recs[0][3] != 0:
             assert all(r[3] == recs[0][3] for r in recs)
+            status = recs[0][3]
             break
         assert all(r[0] == recs[0][0] and r[1] == recs[0][1] for r in recs)
         pairs.append(recs[0][0])
         counts.append(recs[0][1])
         lens.append(sum(r[2] for r in recs))
-    for sh in shards:
+    kept = []
+    for r, sh in enumerate(shards):
         sh.end()
+        if inspect is not None:
+            kept.append(inspect(r, sh.eng))
         sh.eng.close()
+    if inspect is not None:
+        return pairs, counts, lens, kept, status
     return pairs, counts, lens
 
 
@@ -751,27 +787,25 @@ def test_dp_global_count_guard(native):
                 eng.close()
 
 
-def _chain_ranks(native, chunks, nm, world, opts=(), dedup=False):
+def _chain_ranks(native, chunks, nm, world, opts=(), dedup=False, *, shards=None, rank_ids=None, nranks=None,
+                 rank_opts=None, weights=None, inspect=None, timeout=120):
     """bpe_dp_train_cb (the sharded loop of chain steps) on `world` ctxs of the one GPU we have, one thread per rank;
-    the all-reduces are done on the host between barriers.  Returns every rank's result dict."""
+    the all-reduces are done on the host between barriers.  Returns every rank's result dict.
+    shards / rank_ids / nranks / rank_opts / weights: as for _lockstep (rank_opts are set after the common `opts`);
+    timeout: seconds a rank waits at a barrier for its peers; inspect(r, engine) is called after the run, before the
+    engine closes -- with it the return value has a fourth entry, the list of what inspect returned."""
     import threading
     import torch
-    from minbpe_amd.dist import _DevicePtr, shard_chunks
+    from minbpe_amd.dist import _DevicePtr
     dev = torch.device("cuda", 0)
+    parts, rank_ids, nranks, rank_opts, weights = _rank_inputs(chunks, world, shards, rank_ids, nranks, rank_opts, weights)
+    world = len(parts)
     engs = []
-    for r in range(world):
-        lo, hi = shard_chunks(len(chunks), r, world)
-        mine = chunks[lo:hi]
+    for r, mine in enumerate(parts):
         eng = native.Engine(0)
-        for k, v in opts:
+        for k, v in tuple(opts) + tuple(rank_opts[r]):
             eng.set_option(k, v)
-        data = b"".join(mine)
-        offs = np.cumsum([0] + [len(c) for c in mine[:-1]]).astype(np.uint64) if mine else None
-        if dedup:
-            d2, o2, w, _ = native.dedup_chunks(data, offs)
-            eng.load_bytes(d2, o2, w)
-        else:
-            eng.load_bytes(data, offs)
+        _load_shard(native, eng, mine, dedup, weights[r])
         engs.append(eng)
     bar = threading.Barrier(world)
     slot = [None] * world
@@ -783,11 +817,11 @@ def _chain_ranks(native, chunks, nm, world, opts=(), dedup=False):
             t = torch.as_tensor(_DevicePtr(ptr, count, "<i8" if dtype == 1 else "<i4"), device=dev)
             torch.cuda.synchronize()
             slot[r] = (t.cpu().numpy().copy(), count, dtype, op)
-            bar.wait(timeout=120)
+            bar.wait(timeout=timeout)
             assert all(s[1:] == slot[0][1:] for s in slot), [s[1:] for s in slot]  # the same collective on every rank
             stack = np.stack([s[0] for s in slot])
             red = stack.sum(0, dtype=stack.dtype) if op == 0 else stack.min(0)
-            bar.wait(timeout=120)
+            bar.wait(timeout=timeout)
             t.copy_(torch.from_numpy(red))
             torch.cuda.synchronize()
         return allreduce
@@ -796,7 +830,7 @@ def _chain_ranks(native, chunks, nm, world, opts=(), dedup=False):
 
     def run(r):
         try:
-            out[r] = engs[r].dp_train_cb(nm, r, world, make(r))
+            out[r] = engs[r].dp_train_cb(nm, rank_ids[r], nranks, make(r))
         except ValueError as e:
             out[r] = engs[r].last_train
             errs[r] = e
@@ -810,12 +844,15 @@ def _chain_ranks(native, chunks, nm, world, opts=(), dedup=False):
     for t in ths:
         t.join(timeout=300)
     stats = [e.train_stats() for e in engs]
+    hard = [e for e in errs if e is not None and not isinstance(e, ValueError)]
+    kept = [inspect(r, e) for r, e in enumerate(engs)] if inspect is not None and not hard else []
     for e in engs:
         e.close()
-    for e in errs:
-        if e is not None and not isinstance(e, ValueError):
-            raise e
+    for e in hard:
+        raise e
     assert len(set(calls)) == 1, calls
+    if inspect is not None:
+        return out, errs, stats, kept
     return out, errs, stats
 
 
