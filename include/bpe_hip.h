@@ -60,6 +60,8 @@ int bpe_set_stream(bpe_ctx *ctx, void *hip_stream);
  *   "lds_delta" (1), "depth" (8: iterations the host runs ahead), "prof_stride" (64), "merge", "k1",
  *   "chain_kcap" (1..31, default 31: most pairs a sparse chain step merges in one sweep; sharded steps: "dp_kcap",
  *   1..15, default 8), "pool_hint" (0..128, 0 = chain_kcap: the pool is rebuilt when fewer untouched entries are left),
+ *   "chain_aa" (1: a sparse chain step on 256-id slots merges a pair with a == b at the head of its order itself, as a
+ *   batch of one; 0: it hands that merge back to the general path),
  *   "lb_tune", "scan_sup" (1024: the three-pass merge scans the tile summaries of streams of more tiles
  *   than this in three small launches instead of one workgroup);
  *   bpe_decode_batch_resident's copy pass: "dec_copy" (1 staged through an LDS window, 16-byte stores | 0 one token
@@ -282,7 +284,8 @@ int bpe_train_stats(bpe_ctx *ctx, uint64_t *out4);
  * out[8] = chain steps that selected (gathered the pool of pairs anew; the others took their pairs off it), out[9] = ids
  * per slot the stream ended in (1024; 256 once it was re-packed for sparse passes, option "small_slots"), out[10] =
  * chain steps that were ONE launch (selection, merge pass and table update as phases of one resident grid: option
- * "fuse_step").  Writes min(n, 11) values. */
+ * "fuse_step"), out[11] = merges of a pair with a == b that chain steps did themselves (option "chain_aa") instead of
+ * handing them back.  Writes min(n, 12) values. */
 int bpe_train_stats_ex(bpe_ctx *ctx, uint64_t *out, int n);
 
 /* ---- text.encode("utf-8") by all host threads (host, no GPU needed) ------------------ */

@@ -146,6 +146,10 @@ struct bpe_ctx {
     hipEvent_t ev_stage[4] = {nullptr, nullptr, nullptr, nullptr};
     bool stage_busy[4] = {false, false, false, false};  // a copy out of / into the buffer was enqueued: wait for its event before the buffer is touched again
     uint64_t n_fused = 0;                     // chain steps of the last train() that were one launch
+    int chain_aa = 1;                         // option "chain_aa": a sparse chain step on 256-id slots whose order is headed by a pair with a == b merges
+                                              // it itself, as a batch of one (k_chain.hip: merge_aa_wave), instead of handing it back to the
+                                              // general path (0: the hand-back, as in the sharded loop, forced replays, dense steps, 1024-id slots)
+    uint64_t n_aa_chain = 0;                  // a == b merges of the last train() that chain steps did themselves
     unsigned long long *d_step_stamps = nullptr;  // debug (env BPE_STEP_STAMPS=file): clock stamps of its phases, dumped when train() ends
     int pool_hint = 0;                        // option "pool_hint": a rebuild is announced when fewer untouched entries than this are left (0: the step's cap)
     PoolEnt *d_pool = nullptr;                // ... its entries (PL_CAP) and the pairs a rebuild gathers (counter, pad, PL_GATHER x {pair, count})
@@ -1224,6 +1228,11 @@ int launch_chain_step(bpe_ctx *c, uint32_t step, uint32_t zhi, bool use_index, b
     // (the deciding workgroup and the scanning ones wait for each other: all of them must be resident at once -- one
     // 1024-thread workgroup per CU at most, like lean_grid)
     const unsigned nscan = (unsigned)std::max(1, std::min(c->chain_scan, c->num_cus - 1));
+    // a == b at the head of the order: merged by this step itself where its pass can do it -- three launches, the index live
+    // and kept current by a == b passes, 256-id slots, the default engine (lean = 2 forces lean iterations onto every merge:
+    // the variants that cover the hand-back)
+    const bool aa_on = c->chain_aa && !fused && !c->forced && !dense && !dp && c->lean == 1 && c->idx_live && c->aa_sparse &&
+                       c->ts == TILE2_MIN && c->d_desc != nullptr;
     if (fused) {
         // ---- the whole step as ONE launch (k_step.hip) ----------------------------------------------------------------
         if (!c->d_step_pub) {
@@ -1317,7 +1326,7 @@ int launch_chain_step(bpe_ctx *c, uint32_t step, uint32_t zhi, bool use_index, b
         hipLaunchKernelGGL(GK(c, k_pool_sel), dim3(1 + nscan), dim3(1024), 0, c->stream, c->d_rowmax, c->d_mat,
                            c->vcap, c->d_st, stream_ref_h(c), C, c->d_dbits, c->d_lean_res, ++c->lean_tag, c->d_chain_req,
                            kcap, c->d_pool, c->d_pool_gather, hint_below, dp ? c->d_dp_ckey : (long long *)nullptr,
-                           (unsigned long long)(dp ? dp->rank : 0), c->d_pool + PL_CAP);
+                           (unsigned long long)(dp ? dp->rank : 0), c->d_pool + PL_CAP, aa_on ? 1u : 0u);
     LAUNCHCHK(c, "k_pool_sel");
     if (dp) {
         TRY(dp_allreduce(c, c->d_dp_ckey, DP_KEY_WORDS, BPE_DT_INT64, BPE_OP_MIN));
@@ -1356,9 +1365,23 @@ int launch_chain_step(bpe_ctx *c, uint32_t step, uint32_t zhi, bool use_index, b
         const unsigned g1 = std::max(1u, std::min((T + MT / 64 - 1) / (MT / 64), 5u * (unsigned)c->num_cus));
         hipLaunchKernelGGL(GK(c, k_merge_chain_dense1), dim3(g1), dim3(MT), 0, c->stream, A);
     } else {
-        const unsigned g = std::max(1u, std::min(use_index ? nwords : (T + 15) / 16, (unsigned)c->lean_grid));
+        unsigned g = std::max(1u, std::min(use_index ? nwords : (T + 15) / 16, (unsigned)c->lean_grid));
+        ChainAa X;
+        X.sdesc = c->d_desc;
+        X.removed = c->d_removed;
+        X.epoch = 0;
+        X.on = aa_on ? 1u : 0u;
+        if (aa_on) {
+            // (a slot may wait for its predecessor's carry: every workgroup of the pass resident at once, one per CU)
+            g = std::min(g, (unsigned)std::max(1, c->num_cus));
+            if ((++c->epoch & EPOCH_MASK) == 0) {  // tag wrapped: retire every old descriptor (launch_passes2)
+                HIPCHK(c, hipMemsetAsync(c->d_desc, 0, ((TILE / TILE2_MIN) * c->cap_tiles + 4) * sizeof(unsigned long long), c->stream));
+                c->epoch++;
+            }
+            X.epoch = c->epoch;
+        }
         hipLaunchKernelGGL(GK(c, k_merge_chain), dim3(g), dim3(LEAN_MT), 0, c->stream, A, c->d_idx_dirty,
-                           (use_index ? 1u : 0u) | (c->chain_prefetch ? 2u : 0u), c->d_dbits);
+                           (use_index ? 1u : 0u) | (c->chain_prefetch ? 2u : 0u), c->d_dbits, X);
     }
     LAUNCHCHK(c, "k_merge_chain");
     TRY(prof_end(c));
@@ -1375,7 +1398,7 @@ int launch_chain_step(bpe_ctx *c, uint32_t step, uint32_t zhi, bool use_index, b
     hipLaunchKernelGGL(GK(c, k_apply_chain), dim3(na + ncommit), dim3(256), 0, c->stream, c->d_mat, c->vcap, c->d_delta, dl, c->d_rowmax,
                        c->d_st, c->d_dbits, c->par, c->h_rec, c->h_srec, step, na, c->d_hdr2[c->mq], c->d_stage,
                        removed, c->d_smask, nwords, c->d_lean_sum, dp ? c->d_dp_cfold : (const uint32_t *)nullptr, fS,
-                       (const uint32_t *)ftail);
+                       (const uint32_t *)ftail, aa_on ? c->d_removed : (uint32_t *)nullptr);
     LAUNCHCHK(c, "k_apply_chain");
     TRY(prof_end(c));
     c->par ^= 1;

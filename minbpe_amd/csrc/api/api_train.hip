@@ -67,6 +67,7 @@ int bpe_train(bpe_ctx *c, int32_t num_merges, int32_t *pairs_out, uint64_t *coun
     c->n_lean = c->n_deferred = 0;
     c->n_steps = c->n_full = c->n_chained = 0;
     c->n_fused = 0;
+    c->n_aa_chain = 0;
     static const char *stamp_path = getenv("BPE_STEP_STAMPS");
     const size_t stamp_bytes = (size_t)STEP_STAMP_RING * (3 * 16 + 256 * 2) * sizeof(unsigned long long);
     if (stamp_path) {
@@ -370,7 +371,8 @@ int bpe_train(bpe_ctx *c, int32_t num_merges, int32_t *pairs_out, uint64_t *coun
                         return fail(c, BPE_E_INTERNAL, "chain step %u did merges from %u on, the host expected %d", u.step, sr.first_iter, done);
                     for (uint32_t j = 0; j < sr.k && !stop; j++) {
                         TRY(wait_iter((int)(sr.first_iter + j)));
-                        TRY(take_record((int)(sr.first_iter + j), true));
+                        TRY(take_record((int)(sr.first_iter + j), true));  // (an a == b merge of a chain step kept the index current)
+                        if (!stop && c->h_rec[sr.first_iter + j].a == c->h_rec[sr.first_iter + j].b) c->n_aa_chain++;
                     }
                     if (sr.k) {
                         c->n_lean += sr.k;

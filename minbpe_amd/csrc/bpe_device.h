@@ -250,6 +250,14 @@ struct AaArgs {
     uint32_t *idx;            // the index, kept current by this pass (the pairs it creates enter the filters), or nullptr
     uint32_t istride;
 };
+// what a sparse chain step needs beyond AbArgs to merge a pair with a == b itself (k_chain.hip: merge_aa_wave; option
+// "chain_aa")
+struct ChainAa {
+    unsigned long long *sdesc;  // per slot: the carry it published, tagged with the launch (k_merge_aa's descriptors)
+    uint32_t *removed;          // [256] ids removed, always counted: an a == b merge does not remove `count` ids
+    uint32_t epoch;             // this launch's tag
+    uint32_t on;                // 0: a step headed by a == b hands the merge back (the selection was told the same)
+};
 // an entry of the pool (k_pool.hip)
 struct PoolEnt {
     uint32_t xy, c;            // x << 16 | y (training ids are below 65536), the pair's count

@@ -407,6 +407,168 @@ __device__ __forceinline__ void merge_chain_wave(uint32_t *__restrict__ out, uin
     }
 }
 
+// One slot of a chain step whose batch is ONE pair with a == b, by ONE WAVE of the pass's sixteen-wave workgroups: merge_aa_tile
+// (k_slots2.hip) with its workgroup barriers turned into wave barriers and its LDS scratch per wave (scr: 16 words -- the
+// header image tile_rewrite fills, the three halo words).  The algorithm is that pass's: run-parity carry, out-of-place rewrite
+// into the other id buffer, delta format A (replica block by slot number), the index kept current (A.idx), the header staged.
+// The carry walks the run of a's back through the previous slot's words as they stood BEFORE the pass (the rewrite is out of
+// place and headers are staged: nothing a neighbour reads changes under it); only a run that fills the whole previous slot
+// needs that slot's own carry, which every visited slot publishes in X.sdesc under this launch's tag.  That wait ends: such a
+// predecessor holds sites of (a, a), so it is on the list; a workgroup's waves take the list in ascending slot order with no
+// workgroup barrier inside a round, ranges ascend with the workgroup number and workgroups are dispatched in that order -- the
+// lowest slot not yet published never waits for anything, so it publishes, and so on upwards.  The spin is bounded all the
+// same (LOOKBACK_SPINS, then ST_LOOKBACK), as in k_merge_aa.
+// 256-id slots only (MJ == 1: the pass's register budget is 128 per lane).
+__device__ __forceinline__ void merge_aa_wave(uint32_t *scr, const uint32_t t, const AbArgs &A, const ChainAa &X, const uint32_t a,
+                                              const uint32_t newid, const uint32_t Tl) {
+    const int lane = lane_id();
+    uint32_t *s_hdr = scr, *s_halo = scr + 8;
+    uint4 hv6 = (lane & 1) ? make_uint4(INVALID_WORD, INVALID_WORD, 0u, 0u) : make_uint4(INVALID_WORD, INVALID_WORD, INVALID_WORD, 0u);
+    {
+        const long long hi = 2ll * (long long)t - 2 + lane;
+        if (lane < 6 && hi >= 0 && hi < 2ll * (long long)A.T) hv6 = reinterpret_cast<const uint4 *>(A.hdr_in)[hi];
+    }
+    const uint32_t mi = bcast(hv6.w, 2);
+    const int len = (int)(mi & 0x7FFFFFFFu);
+    if (len == 0) return;  // (headers are staged: a slot that stays as it is writes nothing)
+    const uint32_t cur = mi >> 31;
+    const uint32_t *src = (cur ? A.b1 : A.b0) + (size_t)t * TILE2;
+    const uint32_t first = bcast(hv6.x, 2);
+    uint32_t halo0 = bcast(hv6.x, 4), halo1 = bcast(hv6.y, 4), halo2 = bcast(hv6.z, 4);
+    uint32_t prev1 = bcast(hv6.y, 1);
+    uint32_t tnext = t + 1;
+    {
+        const uint32_t nlen = bcast(hv6.w, 4) & 0x7FFFFFFFu, plen = bcast(hv6.w, 0) & 0x7FFFFFFFu;
+        if ((t + 1 < Tl && nlen < 3) || (t > 0 && plen < 2)) {  // (uniform, rare) short or empty neighbours: walk the headers
+            uint32_t ctx[7] = {0, 0, 0, 0, 0, 0, 0};
+            if (lane == 0) slot_context_walk(A.hdr_in, t, Tl, ctx);
+            halo0 = bcast(ctx[0], 0);
+            halo1 = bcast(ctx[1], 0);
+            halo2 = bcast(ctx[2], 0);
+            prev1 = bcast(ctx[4], 0);
+            tnext = bcast(ctx[6], 0);
+        }
+    }
+    const uint32_t hw1 = bcast(hv6.y, 2), hw2 = bcast(hv6.z, 2), hl0 = bcast(hv6.x, 3), hl1 = bcast(hv6.y, 3);
+    if (lane == 0) {
+        s_hdr[0] = first;
+        s_hdr[1] = hw1;
+        s_hdr[2] = hw2;
+        s_hdr[3] = mi;
+        s_hdr[4] = hl0;
+        s_hdr[5] = hl1;
+        s_halo[0] = halo0;
+        s_halo[1] = halo1;
+        s_halo[2] = halo2;
+    }
+    SlotRaw raw;
+    slot_raw_load<true>(raw, src, len);
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    Tile tl;
+    tile_from_slot<true>(tl, raw, len, s_halo);
+    tile_rbits(tl, a, a);
+    uint32_t s = (uint32_t)((prev1 != INVALID_WORD) & ((prev1 & IDMASK) == a) & ((first & NWMASK) == a));
+    {
+        // the carry is the PARITY of the run of a's that ends at the previous slot's last id (F2): merge_aa_tile's walk, every
+        // value below uniform over the wave
+        const unsigned long long tag = ((unsigned long long)(X.epoch & EPOCH_MASK)) << 42;
+        uint32_t sc = 0;
+        bool failed = false;
+        if (s) {  // the boundary pair matches: r[last of previous slot] = 1
+            uint32_t u = t;
+            uint32_t mu = 0;
+            while (u-- > 0) {
+                mu = A.hdr_in[u].meta;
+                if (mu & 0x7FFFFFFFu) break;
+            }
+            const int lu = (int)(mu & 0x7FFFFFFFu);
+            const uint32_t *pu = ((mu >> 31) ? A.b1 : A.b0) + (size_t)u * TILE2;
+            int ones = 0;       // r-ones counted so far, walking back from the last id
+            bool open = true;   // no zero met yet
+            uint32_t nextw = first;  // the word after the current position
+            for (int base = lu - 1; base >= 0 && open; base -= 64) {
+                const int q = base - lane;
+                const uint32_t xq = (q >= 0) ? pu[q] : INVALID_WORD;
+                uint32_t nx = (uint32_t)__shfl_up((int)xq, 1);
+                if (lane == 0) nx = nextw;
+                const bool r = (q >= 0) && ((xq & IDMASK) == a) && ((nx & NWMASK) == a);
+                const unsigned long long zeros = __ballot(!r);
+                if (zeros) {
+                    ones += __ffsll((long long)zeros) - 1;
+                    // a zero caused by running off the slot (q < 0) means the whole slot is ones
+                    const int zl = __ffsll((long long)zeros) - 1;
+                    open = (base - zl < 0);
+                    break;
+                }
+                ones += 64;
+                nextw = (uint32_t)__shfl((int)xq, 63);
+            }
+            if (!open || ones < lu) {
+                sc = (uint32_t)(ones & 1);  // m[last] = r[last] & (run length odd)
+            } else {
+                // the whole previous slot is one run: m[q] = (q even) ^ its carry
+                uint32_t su = 0;
+                bool got = false;
+                for (uint32_t spins = 0; spins < LOOKBACK_SPINS; spins++) {
+                    const unsigned long long d = desc_load(&X.sdesc[u]);
+                    if ((d >> 42) == (tag >> 42) + (1ull << 20)) {  // status bit above the epoch
+                        su = (uint32_t)(d & 1u);
+                        got = true;
+                        break;
+                    }
+                    __builtin_amdgcn_s_sleep(8);
+                }
+                failed = !got;
+                sc = (uint32_t)(((lu - 1) & 1) == 0) ^ su;
+            }
+        }
+        if (lane == 0) {
+            desc_store(&X.sdesc[t], tag | (1ull << 62) | sc);
+            if (failed) atomicExch(&A.st->status, ST_LOOKBACK);
+        }
+        s = sc;
+    }
+    // fast path: no match at any owned position, none at the first word after the slot, no carry
+    {
+        uint32_t anyr = s;
+        const int q0 = lane * 4;
+        const int nb = len + 1 - q0;  // keep the bits of positions q <= len
+        const uint32_t keep = nb >= 4 ? 0xFu : (nb <= 0 ? 0u : ((1u << nb) - 1u));
+        anyr |= tl.rb[0] & keep;
+        // a full slot: the word after it is the wave's tail, not one of my registers
+        if (len == TILE2) anyr |= (uint32_t)(((tl.tail[0] & IDMASK) == a) & ((tl.tail[1] & NWMASK) == a));
+        if (!__any(anyr != 0)) return;
+    }
+    tile_lzscan<true>(tl, nullptr);
+    uint32_t kept = 0;
+    bool changed = false;
+    uint32_t *dst = (cur ? A.b0 : A.b1) + (size_t)t * TILE2;  // the OTHER buffer
+    tile_rewrite<true, true, 1, true>(tl, s, a, a, newid, dst, nullptr, A.delta, A.vcap, len, &kept, &changed, s_hdr, A.idx,
+                                      A.istride, t, tnext, t);
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    if (lane == 0 && changed) {
+        uint32_t h[8];
+        h[0] = kept > 0 ? s_hdr[0] : INVALID_WORD;  // fewer than 3 ids left
+        h[1] = kept > 1 ? s_hdr[1] : INVALID_WORD;
+        h[2] = kept > 2 ? s_hdr[2] : INVALID_WORD;
+        h[3] = kept | ((cur ^ 1u) << 31);
+        h[4] = kept > 1 ? s_hdr[4] : INVALID_WORD;
+        h[5] = kept > 0 ? s_hdr[5] : INVALID_WORD;
+        h[6] = h[7] = 0;
+        stage_put<false>(A.stage + t, t, h);
+        atomicOr(&A.smask[t >> 5], 1u << (t & 31));
+        atomicAdd(&X.removed[(t & 255u) * REMOVED_STRIDE], (uint32_t)len - kept);
+        if (kept < 3 && t + 1 < Tl) A.st->gap = 1;
+    }
+    // (the wave's next slot reuses scr)
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+}
+
 // The look-up table of a batch's first tokens (merge_chain_wave): one wave looks for a multiplier m (odd, 129 .. 255) under
 // which no two of the K tokens fall into the same of the 256 buckets (K = 15: two in three multipliers do, K = 31: one in
 // six -- none of the 64 about once in 10^5 batches); returns it to every lane (0: none found, or a batch too small to pay
@@ -475,7 +637,7 @@ __device__ __forceinline__ void merge_chain_body(const AbArgs &A, const uint32_t
                                                  MergeLds &L, const uint32_t K, const uint32_t z0, const uint32_t brep,
                                                  const uint32_t blk, const uint32_t nblk, unsigned long long *dbg = nullptr,
                                                  const bool have_st = false, const uint32_t tlive_in = 0, const uint32_t gap_in = 0,
-                                                 const bool pre_ok = false, const uint32_t pre_hm = 0) {
+                                                 const bool pre_ok = false, const uint32_t pre_hm = 0, const ChainAa *X = nullptr) {
     auto dstamp = [&](int i) {  // (debug, BPE_STEP_STAMPS)
         if (dbg && threadIdx.x == 0) dbg[i] = wall_clock64();
     };
@@ -497,7 +659,16 @@ __device__ __forceinline__ void merge_chain_body(const AbArgs &A, const uint32_t
     AbArgs A1 = A;
     A1.newid = z0;
     const uint32_t a0 = s_pa[0], b0 = s_pb[0];
+    // a batch of one with a == b (the selection forms it only where the host enabled it, X->on): the slot goes through the
+    // a == b rewrite (merge_aa_wave).  256-id slots only.
+    const bool aa = MJ == 1 && X != nullptr && X->on && K == 1 && a0 == b0;
     auto do_slot = [&](uint32_t t) {
+        if constexpr (MJ == 1) {
+            if (aa) {  // (uniform)
+                merge_aa_wave(s_out[wave_id()], t, A, *X, a0, z0, Tl);
+                return;
+            }
+        }
         if (K == 1) {
             merge_ab_wave<true, true, false, THROUGH>(s_out[wave_id()], nullptr, t, A1, a0, b0, Tl);
         } else {
@@ -525,6 +696,20 @@ __device__ __forceinline__ void merge_chain_body(const AbArgs &A, const uint32_t
                 pair_hash(s_pa[p], s_pb[p], h1, h2, h3);
                 mk |= A.idx[(size_t)h1 * A.istride + w] & A.idx[(size_t)h2 * A.istride + w] &
                       A.idx[(size_t)h3 * A.istride + w];
+            }
+            if (aa) {
+                // build_cand_list's a == b rule (k_index.hip): the pass charges every pair to its LEFT element, so the slot
+                // before a candidate owes table updates too -- slot s is visited if s or s + 1 is a candidate or marked.
+                // The bit of slot 32 w + 32 is in the NEXT mask word, which may be another thread's, another round's or
+                // another workgroup's: every thread fetches it for itself.
+                uint32_t nx = 0;
+                if (w + 1 < nwords) {
+                    uint32_t h1, h2, h3;
+                    pair_hash(a0, a0, h1, h2, h3);
+                    nx = idx_dirty[w + 1] | (A.idx[(size_t)h1 * A.istride + w + 1] & A.idx[(size_t)h2 * A.istride + w + 1] &
+                                             A.idx[(size_t)h3 * A.istride + w + 1]);
+                }
+                mk |= (mk >> 1) | (nx << 31);
             }
             const uint32_t left = Tl - w * 32;
             if (left < 32) mk &= (1u << left) - 1u;
@@ -594,7 +779,7 @@ __device__ __forceinline__ void step_words_fetch(const DevState *st, uint32_t *s
     __syncthreads();
 }
 __global__ void __launch_bounds__(LEAN_MT)
-k_merge_chain(AbArgs A, const uint32_t *__restrict__ idx_dirty, uint32_t use_index, uint32_t *__restrict__ dbits) {
+k_merge_chain(AbArgs A, const uint32_t *__restrict__ idx_dirty, uint32_t use_index, uint32_t *__restrict__ dbits, ChainAa X) {
     __shared__ MergeLds L;
     __shared__ uint32_t s_w[SW_WORDS];
     DevState *st = A.st;
@@ -616,8 +801,13 @@ k_merge_chain(AbArgs A, const uint32_t *__restrict__ idx_dirty, uint32_t use_ind
         if (threadIdx.x == 0) L.s_pb1[0] = 0xFFFFFFFFu;  // (a masked word has its weight bits clear: never equal)
     }
     __syncthreads();
+    // (a == b heads the batch although the host left the a == b pass off: the selection and this launch disagree)
+    if (K == 1 && s_w[0] == s_w[SW_BB] && !(MJ == 1 && X.on)) {
+        if (blockIdx.x == 0 && threadIdx.x == 0) atomicExch(&st->status, ST_INTERNAL);
+        return;
+    }
     merge_chain_body(A, idx_dirty, use_index, L, K, z0, brep, blockIdx.x, gridDim.x, nullptr, true, s_w[SW_TLIVE], s_w[SW_GAP],
-                     s_w[SW_BHM_KEY] == ((z0 << 8) | K), s_w[SW_BHM]);
+                     s_w[SW_BHM_KEY] == ((z0 << 8) | K), s_w[SW_BHM], &X);
 }
 
 // ---------------------------------------------------------------------------
@@ -751,7 +941,38 @@ __device__ __forceinline__ void apply_chain_tokens(const uint32_t t, uint32_t *_
             rm = reinterpret_cast<const uint2 *>(rowmax)[t];
         }
         bool flagged = false;
-        if (K == 1) {
+        if (!OWNED && K == 1 && pair_a(0) == pair_b(0)) {
+            // ---- one pair with a == b (merge_aa_wave): delta format A, what k_apply2 applies for such a merge -- pairs (t, a)
+            // destroyed, (a, t) destroyed, (t, Z) created, (Z, t) created, in vectors 0..3 of all nrep replica blocks; no adj
+            const uint32_t a = pair_a(0), Z = z0;
+            constexpr int RB = 4;  // replicas in flight at a time (four vectors each)
+            uint32_t acc[4] = {0, 0, 0, 0};
+            const uint32_t old_ta = live ? mat[(size_t)t * stride + a] : 0u;
+            for (uint32_t r0 = 0; r0 < nrep; r0 += RB) {  // (uniform)
+                uint32_t x[RB][4];
+#pragma unroll
+                for (int k = 0; k < RB; k++)
+#pragma unroll
+                    for (int v = 0; v < 4; v++)
+                        x[k][v] = (live && r0 + k < nrep) ? delta[delta_rep_off(r0 + k, vc) + (size_t)v * vc + t] : 0u;
+#pragma unroll
+                for (int k = 0; k < RB; k++)
+#pragma unroll
+                    for (int v = 0; v < 4; v++) {
+                        if (x[k][v]) delta[delta_rep_off(r0 + k, vc) + (size_t)v * vc + t] = 0;
+                        acc[v] += x[k][v];
+                    }
+            }
+            if (acc[0]) {
+                atomicSub(&mat[(size_t)t * stride + a], acc[0]);
+                flagged |= old_ta == rm.x;  // ((t, Z) <= what (t, a) lost: every (t, Z) stands where a (t, a) stood)
+            }
+            if (acc[1]) atomicSub(&mat[(size_t)a * stride + t], acc[1]);
+            if (acc[2]) atomicAdd(&mat[(size_t)t * stride + Z], acc[2]);
+            if (acc[3]) atomicAdd(&mat[(size_t)Z * stride + t], acc[3]);
+            if (live && t == a) mat[(size_t)a * stride + a] = 0;  // no (a, a) survives the merge (F2), whatever the bookkeeping left
+            flagged |= live && ((t == a) | (t == Z));
+        } else if (K == 1) {
             // ---- one pair: all nrep replicas, (t,a) loaded up front (no returning atomic) ----------------
             const uint32_t a = pair_a(0), b = pair_b(0), Z = z0;
             const uint32_t adj = folded ? ftail[0] : adjs[0];  // (merge_ab_wave's adj)
@@ -891,8 +1112,12 @@ __device__ __forceinline__ void apply_chain_tokens(const uint32_t t, uint32_t *_
 // removal counters, filled by every workgroup's device atomics earlier in the same launch, are read at agent scope)
 __device__ __forceinline__ void apply_chain_records(DevState *st, int par, IterRec *rec, StepRec *srec, uint32_t step,
                                                     uint32_t *__restrict__ removed, const uint32_t K, const bool noop,
-                                                    const uint32_t status, const uint32_t defer, const uint32_t remote) {
+                                                    const uint32_t status, const uint32_t defer, const uint32_t remote,
+                                                    uint32_t *__restrict__ removed_aa = nullptr) {
     {
+        // (a batch of one with a == b: its pass always counts the ids it removes -- `count` pairs are not `count` sites
+        // in a run -- in the counters the host names for it)
+        if (removed_aa && !noop && K == 1 && st->ba[0] == st->bb[0]) removed = removed_aa;
         // ids removed by the merge pass: CH_RMV counters per pair of the batch, one per 256-byte line (lane l: counters
         // 4l .. 4l + 3, all of pair l / 2)
         // (removed == nullptr: an unweighted stream -- a merge of a != b removes exactly as many ids as the pair counts, base.py:25-41:
@@ -990,7 +1215,8 @@ k_apply_chain(uint32_t *__restrict__ mat, uint32_t stride, uint32_t *__restrict_
               const uint32_t *__restrict__ rowmax, DevState *st, uint32_t *__restrict__ dbits, int par, IterRec *rec,
               StepRec *srec, uint32_t step, uint32_t na, SlotHdr *__restrict__ hdr_cur, const StageRec *__restrict__ stage,
               uint32_t *__restrict__ removed, uint32_t *__restrict__ smask, uint32_t nwords, uint4 *__restrict__ sums,
-              const uint32_t *__restrict__ folded, uint32_t fS, const uint32_t *__restrict__ ftail) {
+              const uint32_t *__restrict__ folded, uint32_t fS, const uint32_t *__restrict__ ftail,
+              uint32_t *__restrict__ removed_aa) {
     // folded != nullptr (sharded training): the batch's delta is the all-reduced payload of k_dp_fold_chain -- pair p's
     // SL at folded[2p fS ..), SR at folded[(2p + 1) fS ..), its adj in ftail[p] -- instead of this rank's replica blocks
     // (sharded: ftail[16] = the number of ranks whose status was raised when they folded this step's delta -- a
@@ -1010,7 +1236,7 @@ k_apply_chain(uint32_t *__restrict__ mat, uint32_t stride, uint32_t *__restrict_
                                   ftail, K, z0, 0u, s_pairs, s_w + SW_BADJ, s_w[SW_BREP]);
         return;
     }
-    if (blockIdx.x == na && threadIdx.x < 64) apply_chain_records(st, par, rec, srec, step, removed, K, noop, status, defer, remote);
+    if (blockIdx.x == na && threadIdx.x < 64) apply_chain_records(st, par, rec, srec, step, removed, K, noop, status, defer, remote, removed_aa);
     if (noop) return;
     apply_chain_commit((blockIdx.x - na) * blockDim.x + threadIdx.x, (gridDim.x - na) * blockDim.x, nwords, smask, stage, hdr_cur);
 }

@@ -57,8 +57,11 @@ struct SlotRaw {
     uint4 v[MJ];
     uint32_t tail[3];
 };
+// (W1, here and in the tile helpers below: the caller is ONE wave of a larger workgroup and the slot is that wave's span
+// -- a chain step's a == b pass, k_chain.hip: wave number 0 whatever wave_id() says, no workgroup barrier, no LDS exchange)
+template <bool W1 = false>
 __device__ __forceinline__ void slot_raw_load(SlotRaw &r, const uint32_t *__restrict__ src, int len) {
-    const int lane = lane_id(), wrel = wave_id() * WAVE_SPAN;
+    const int lane = lane_id(), wrel = W1 ? 0 : wave_id() * WAVE_SPAN;
 #pragma unroll
     for (int j = 0; j < MJ; j++) {
         const int q0 = wrel + j * 256 + lane * 4;
@@ -71,8 +74,9 @@ __device__ __forceinline__ void slot_raw_load(SlotRaw &r, const uint32_t *__rest
         r.tail[i] = (q < len) ? src[q] : 0u;
     }
 }
+template <bool W1 = false>
 __device__ __forceinline__ void tile_from_slot(Tile &t, const SlotRaw &r, int len, const uint32_t *halo) {
-    const int lane = lane_id(), wrel = wave_id() * WAVE_SPAN;
+    const int lane = lane_id(), wrel = W1 ? 0 : wave_id() * WAVE_SPAN;
 #pragma unroll
     for (int j = 0; j < MJ; j++) {
         const int q0 = wrel + j * 256 + lane * 4;
@@ -112,8 +116,9 @@ __device__ __forceinline__ void tile_rbits(Tile &t, uint32_t a, uint32_t b) {
 }
 // exclusive max-scan of "index of the last zero of r" in (wave, stripe, lane) order:
 // everything the m bits need (contains one __syncthreads)
+template <bool W1 = false>
 __device__ __forceinline__ void tile_lzscan(Tile &t, int *s_wave) {
-    const int lane = lane_id(), wave = wave_id();
+    const int lane = lane_id(), wave = W1 ? 0 : wave_id();
     int lzg[MJ];
     const int gb0 = wave * WAVE_SPAN + lane * 4;
 #pragma unroll
@@ -129,6 +134,7 @@ __device__ __forceinline__ void tile_lzscan(Tile &t, int *s_wave) {
         t.E[j] = max(carry, ex);
         carry = max(carry, (int)lane_last((uint32_t)v));
     }
+    if (W1) return;
     if (lane == 0) s_wave[wave] = carry;
     __syncthreads();
     int win = -1;
@@ -154,8 +160,9 @@ __device__ __forceinline__ uint32_t parity_bit(int q, int lz, uint32_t s) {
 }
 
 // m bits (4) of my group in stripe j, and mprev = m of the element before it.
+template <bool W1 = false>
 __device__ __forceinline__ uint32_t group_mbits(const Tile &t, int j, uint32_t s, uint32_t &mprev) {
-    const int q0 = wave_id() * WAVE_SPAN + j * 256 + lane_id() * 4;
+    const int q0 = (W1 ? 0 : wave_id() * WAVE_SPAN) + j * 256 + lane_id() * 4;
     int lz = t.E[j];
     // predecessor q0-1: r = 1 unless it is the last zero itself
     mprev = (q0 == 0) ? s : ((lz == q0 - 1) ? 0u : parity_bit(q0 - 1, lz, s));
@@ -523,21 +530,23 @@ k_tile_expand(const uint64_t *__restrict__ tsum, uint64_t ntiles, const DevState
 // the slot simply stays where it is).  *kept_out / *changed_out: block totals.
 // HL: layout behind hdr4 -- 0: {first three, last}; 1: a SlotHdr image {first three, (meta),
 // second-to-last, last} (k_slots2.hip; hdr4 may then point into LDS).
-template <bool DELTA, bool SKIP_UNCHANGED, int HL = 0>
+// W1: see slot_raw_load; rep_sel: which replica block of the delta vectors (default: by workgroup).
+template <bool DELTA, bool SKIP_UNCHANGED, int HL = 0, bool W1 = false>
 __device__ __forceinline__ void tile_rewrite(const Tile &t, uint32_t s, uint32_t a, uint32_t b,
                                              uint32_t newid, uint32_t *__restrict__ dst_tile,
                                              uint32_t *s_wsum, uint32_t *__restrict__ delta,
                                              uint32_t vcap, int own_len, uint32_t *kept_out,
                                              bool *changed_out, uint32_t *__restrict__ hdr4 = nullptr,
                                              uint32_t *__restrict__ idx = nullptr, uint32_t istride = 0,
-                                             uint32_t tself = 0, uint32_t tnext = 0xFFFFFFFFu) {
-    const int lane = lane_id(), wave = wave_id();
+                                             uint32_t tself = 0, uint32_t tnext = 0xFFFFFFFFu,
+                                             uint32_t rep_sel = 0xFFFFFFFFu) {
+    const int lane = lane_id(), wave = W1 ? 0 : wave_id();
     uint32_t mb[MJ], mp[MJ], kb[MJ], ex[MJ];
     uint32_t carry = 0, chg = 0;
     const int qw = wave * WAVE_SPAN + lane * 4;
 #pragma unroll
     for (int j = 0; j < MJ; j++) {
-        mb[j] = group_mbits(t, j, s, mp[j]);
+        mb[j] = group_mbits<W1>(t, j, s, mp[j]);
         // kept bit k = !m[k-1], only for owned positions
         uint32_t valid = 0;
 #pragma unroll
@@ -549,15 +558,20 @@ __device__ __forceinline__ void tile_rewrite(const Tile &t, uint32_t s, uint32_t
         carry += lane_last(v);
     }
     const bool wchg = __any(chg != 0);
-    if (lane == 0) s_wsum[wave] = carry | (wchg ? 0x80000000u : 0u);
-    __syncthreads();
     uint32_t wbase = 0, total = 0;
     bool changed = (s != 0);
-    for (int w = 0; w < MT / 64; w++) {
-        const uint32_t v = s_wsum[w];
-        if (w < wave) wbase += v & 0x7FFFFFFFu;
-        total += v & 0x7FFFFFFFu;
-        changed |= (v >> 31) != 0;
+    if (W1) {
+        total = carry;
+        changed |= wchg;
+    } else {
+        if (lane == 0) s_wsum[wave] = carry | (wchg ? 0x80000000u : 0u);
+        __syncthreads();
+        for (int w = 0; w < MT / 64; w++) {
+            const uint32_t v = s_wsum[w];
+            if (w < wave) wbase += v & 0x7FFFFFFFu;
+            total += v & 0x7FFFFFFFu;
+            changed |= (v >> 31) != 0;
+        }
     }
     if (kept_out) *kept_out = total;
     if (changed_out) *changed_out = changed;
@@ -616,7 +630,7 @@ __device__ __forceinline__ void tile_rewrite(const Tile &t, uint32_t s, uint32_t
         // same-address atomics serialise (~11 ns each): spread them over replicas
         const uint32_t nrep = 1u << (vcap >> 24);  // host packs log2(replicas) above the stride
         vcap &= 0xFFFFFFu;
-        delta += delta_rep_off(blockIdx.x & (nrep - 1), vcap);
+        delta += delta_rep_off((rep_sel != 0xFFFFFFFFu ? rep_sel : blockIdx.x) & (nrep - 1), vcap);
 #pragma unroll
         for (int j = 0; j < MJ; j++) {
             const uint32_t nb_m = lane_next(mb[j], 0);

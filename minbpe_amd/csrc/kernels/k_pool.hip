@@ -160,7 +160,7 @@ __device__ __forceinline__ void pool_finish(DevState *st, PoolEnt *__restrict__ 
                                             unsigned long long *a_key, const uint32_t *s_ls, const uint32_t *s_le,
                                             uint32_t *s_dirty, uint32_t *s_clash, uint32_t *s_k, uint32_t *s_unt, uint32_t n,
                                             uint32_t kmax, uint32_t iter, uint32_t theta, unsigned long long epoch, bool rebuilt,
-                                            uint32_t hint_below, int ksh, PoolScratch &X) {
+                                            uint32_t hint_below, int ksh, PoolScratch &X, const bool aa_ok = false) {
     const uint32_t tid = threadIdx.x;
     const uint32_t nwalk = min(n, kmax);
     // ---- the order inside every level: by key (a level whose keys are not of one epoch stays without an order) ----------
@@ -208,13 +208,16 @@ __device__ __forceinline__ void pool_finish(DevState *st, PoolEnt *__restrict__ 
         const uint32_t x = a_xy[i] >> 16, y = a_xy[i] & 0xFFFFu;
         bool bad = false;
         if (j == i) {
-            bad = (x == y) | (s_dirty[i] != 0);
+            // (aa_ok: the merge pass of this step does a == b itself -- at the HEAD of the order such a pair is a batch of
+            // one; further down it still ends the batch before it)
+            bad = ((x == y) & !(aa_ok && i == 0)) | (s_dirty[i] != 0);
         } else if (j < i) {
             const uint32_t xj = a_xy[j] >> 16, yj = a_xy[j] & 0xFFFFu;
+            if (j == 0 && xj == yj) bad = true;  // (the batch of one: nothing joins it)
             // (a SECOND token may be shared: sites of (a, b) and (c, b) never overlap and neither merge moves the
             // other's count -- only a pair that could chain onto a site of the batch, x a second token or y a first
             // one, stops the walk; first tokens stay distinct: the merge pass looks a pair up by its first token)
-            bad = (xj == x) | (xj == y) | (yj == x);
+            bad |= (xj == x) | (xj == y) | (yj == x);
         }
         if (bad) atomicOr(&X.bad, 1u << i);
     }
@@ -270,13 +273,17 @@ __device__ __forceinline__ void pool_finish(DevState *st, PoolEnt *__restrict__ 
         }
     }
     // ---- the rest is the next step's pool ----------------------------------------------------------------------------------
+    // (a batch of one with a == b stays in the pool as an entry: what a run of a's leaves -- (Z, Z), (Z, a) -- stood where
+    // (a, a) stood and has no other predecessor among the entries; the next selection's maintenance looks its four variants
+    // up like any entry's, and (a, a) itself, now zero, drops out there)
+    const uint32_t Kout = (K == 1 && (a_xy[0] >> 16) == (a_xy[0] & 0xFFFFu)) ? 0u : K;
     bool unt = false;
-    if (tid >= K && tid < n) {
+    if (tid >= Kout && tid < n) {
         PoolEnt e2;
         e2.xy = a_xy[tid];
         e2.c = a_c[tid];
         e2.key = a_key[tid];
-        pool[tid - K] = e2;
+        pool[tid - Kout] = e2;
         const uint32_t x = e2.xy >> 16, y = e2.xy & 0xFFFFu;
         bool touched = false;
 #pragma unroll 4
@@ -289,7 +296,7 @@ __device__ __forceinline__ void pool_finish(DevState *st, PoolEnt *__restrict__ 
     }
     __syncthreads();
     if (tid == 0) {
-        st->pool_n = n - K;
+        st->pool_n = n - Kout;
         st->pool_theta = theta;
         st->pool_epoch = epoch;
         st->pool_hint_next = *s_unt < hint_below ? 1u : 0u;
@@ -319,7 +326,7 @@ pool_sel_body(uint32_t *__restrict__ rowmax, uint32_t *__restrict__ mat, uint32_
               const CandArgs &C, uint32_t *__restrict__ dbits, unsigned long long *__restrict__ res, uint32_t tag,
               unsigned long long *__restrict__ req, uint32_t kcap, PoolEnt *__restrict__ pool, uint32_t *__restrict__ gather,
               uint32_t hint_below, long long *__restrict__ dpkey, unsigned long long dprank, PoolEnt *__restrict__ mid,
-              PoolLds &L, const uint32_t blk, const uint32_t nblk, unsigned long long *dbg = nullptr) {
+              PoolLds &L, const uint32_t blk, const uint32_t nblk, unsigned long long *dbg = nullptr, const bool aa_ok = false) {
     auto dstamp = [&](int i) {  // (debug, BPE_STEP_STAMPS: where a selection's time goes)
         if (dbg && threadIdx.x == 0 && blk == 0) dbg[i] = wall_clock64();
     };
@@ -863,7 +870,7 @@ pool_sel_body(uint32_t *__restrict__ rowmax, uint32_t *__restrict__ mat, uint32_
     }
     dstamp(13);
     pool_finish(st, pool, b_xy, b_c, b_key, a_xy, a_c, a_key, s_ls, s_le, s_dirty, s_clash, &s_k, &s_unt, n, kmax, iter, theta,
-                epoch, rebuilt, hint_below, PL_KSH, X);
+                epoch, rebuilt, hint_below, PL_KSH, X, aa_ok);
     dstamp(14);
 }
 
@@ -871,10 +878,11 @@ __global__ void __launch_bounds__(1024)
 k_pool_sel(uint32_t *__restrict__ rowmax, uint32_t *__restrict__ mat, uint32_t stride, DevState *st, SlotRefH ref,
            CandArgs C, uint32_t *__restrict__ dbits, unsigned long long *__restrict__ res, uint32_t tag,
            unsigned long long *__restrict__ req, uint32_t kcap, PoolEnt *__restrict__ pool, uint32_t *__restrict__ gather,
-           uint32_t hint_below, long long *__restrict__ dpkey, unsigned long long dprank, PoolEnt *__restrict__ mid) {
+           uint32_t hint_below, long long *__restrict__ dpkey, unsigned long long dprank, PoolEnt *__restrict__ mid,
+           uint32_t aa_ok) {
     __shared__ PoolLds L;
     pool_sel_body(rowmax, mat, stride, st, ref, C, dbits, res, tag, req, kcap, pool, gather, hint_below, dpkey, dprank, mid, L,
-                  blockIdx.x, gridDim.x);
+                  blockIdx.x, gridDim.x, nullptr, aa_ok != 0);
 }
 
 // k_pool_sel_dp: the second half of a sharded selection, after the MIN all-reduce of the first occurrences (one workgroup
