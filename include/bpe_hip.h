@@ -62,6 +62,11 @@ int bpe_set_stream(bpe_ctx *ctx, void *hip_stream);
  *   1..15, default 8), "pool_hint" (0..128, 0 = chain_kcap: the pool is rebuilt when fewer untouched entries are left),
  *   "chain_aa" (1: a sparse chain step on 256-id slots merges a pair with a == b at the head of its order itself, as a
  *   batch of one; 0: it hands that merge back to the general path),
+ *   "chain_share_first" (1: the batch of a single-GPU job's three-launch chain step may hold a first token twice --
+ *   (a, b1), (a, b2), whose sites never overlap --, its merge pass finds a site by its pair; 0: first tokens stay
+ *   distinct, as they always do in sharded steps, one-launch steps and forced replays; the results are the same),
+ *   "chain_hash_kmin" (0 = 2: the smallest batch whose merge pass looks a site up in the pair table; 32: never --
+ *   every position is compared with every pair, the exact fall-back of a batch without a collision-free multiplier),
  *   "lb_tune", "scan_sup" (1024: the three-pass merge scans the tile summaries of streams of more tiles
  *   than this in three small launches instead of one workgroup);
  *   bpe_decode_batch_resident's copy pass: "dec_copy" (1 staged through an LDS window, 16-byte stores | 0 one token
@@ -285,7 +290,8 @@ int bpe_train_stats(bpe_ctx *ctx, uint64_t *out4);
  * per slot the stream ended in (1024; 256 once it was re-packed for sparse passes, option "small_slots"), out[10] =
  * chain steps that were ONE launch (selection, merge pass and table update as phases of one resident grid: option
  * "fuse_step"), out[11] = merges of a pair with a == b that chain steps did themselves (option "chain_aa") instead of
- * handing them back.  Writes min(n, 12) values. */
+ * handing them back, out[12] = chain steps whose batch held a first token twice (option "chain_share_first").
+ * Writes min(n, 13) values. */
 int bpe_train_stats_ex(bpe_ctx *ctx, uint64_t *out, int n);
 
 /* ---- text.encode("utf-8") by all host threads (host, no GPU needed) ------------------ */

@@ -570,12 +570,14 @@ class Engine:
         general path, merges that needed no selection of their own, chain steps, chain steps that selected; slot_ids = ids per
         slot the stream ended in (1024, or 256 once it was re-packed for sparse passes); fused_steps = chain steps that were
         one launch (k_step.hip); aa_in_chain = merges of a pair with a == b that chain steps did themselves (option
-        "chain_aa") instead of handing them back."""
-        out = np.zeros(12, np.uint64)
-        self._check(_lib.bpe_train_stats_ex(self._h, _ptr(out), 12))
+        "chain_aa") instead of handing them back; shared_first = chain steps whose batch held a first token twice (option
+        "chain_share_first")."""
+        out = np.zeros(13, np.uint64)
+        self._check(_lib.bpe_train_stats_ex(self._h, _ptr(out), 13))
         return dict(dense=int(out[0]), sparse=int(out[1]), index_builds=int(out[2]), slots=int(out[3]),
                     lean=int(out[4]), deferred=int(out[5]), chained=int(out[6]), steps=int(out[7]),
-                    selections=int(out[8]), slot_ids=int(out[9]), fused_steps=int(out[10]), aa_in_chain=int(out[11]))
+                    selections=int(out[8]), slot_ids=int(out[9]), fused_steps=int(out[10]), aa_in_chain=int(out[11]),
+                    shared_first=int(out[12]))
 
     def prof_read(self):
         k = len(PROF_KINDS)

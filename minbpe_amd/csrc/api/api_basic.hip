@@ -201,6 +201,12 @@ int bpe_set_option(bpe_ctx *c, const char *name, int64_t value) {
     } else if (!strcmp(name, "chain_aa")) {
         if (value < 0 || value > 1) return fail(c, BPE_E_ARG, "chain_aa must be 0 or 1");
         c->chain_aa = (int)value;
+    } else if (!strcmp(name, "chain_share_first")) {
+        if (value < 0 || value > 1) return fail(c, BPE_E_ARG, "chain_share_first must be 0 or 1");
+        c->chain_share_first = (int)value;
+    } else if (!strcmp(name, "chain_hash_kmin")) {
+        if (value < 0 || value > 32) return fail(c, BPE_E_ARG, "chain_hash_kmin must be 0..32");
+        c->chain_hash_kmin = (int)value;
     } else if (!strcmp(name, "pool_hint")) {
         if (value < 0 || value > 128) return fail(c, BPE_E_ARG, "pool_hint must be 0..128");
         c->pool_hint = (int)value;

@@ -150,6 +150,12 @@ struct bpe_ctx {
                                               // it itself, as a batch of one (k_chain.hip: merge_aa_wave), instead of handing it back to the
                                               // general path (0: the hand-back, as in the sharded loop, forced replays, dense steps, 1024-id slots)
     uint64_t n_aa_chain = 0;                  // a == b merges of the last train() that chain steps did themselves
+    int chain_share_first = 1;                // option "chain_share_first": a chain step's batch may hold a first token twice -- (a, b1), (a, b2); the
+                                              // merge pass finds a site by its pair (k_chain.hip: merge_chain_wave).  0: first tokens stay distinct, as
+                                              // in the sharded loop, forced replays and the one-launch step
+    int chain_hash_kmin = 0;                  // option "chain_hash_kmin": the smallest batch whose merge pass uses the pair look-up table (0: the
+                                              // kernels' own, 2); 32 = never: every position is compared with every pair (the exact fall-back)
+    uint64_t n_shared_first = 0;              // chain steps of the last train() whose batch held a first token twice
     unsigned long long *d_step_stamps = nullptr;  // debug (env BPE_STEP_STAMPS=file): clock stamps of its phases, dumped when train() ends
     int pool_hint = 0;                        // option "pool_hint": a rebuild is announced when fewer untouched entries than this are left (0: the step's cap)
     PoolEnt *d_pool = nullptr;                // ... its entries (PL_CAP) and the pairs a rebuild gathers (counter, pad, PL_GATHER x {pair, count})
@@ -1233,6 +1239,10 @@ int launch_chain_step(bpe_ctx *c, uint32_t step, uint32_t zhi, bool use_index, b
     // the variants that cover the hand-back)
     const bool aa_on = c->chain_aa && !fused && !c->forced && !dense && !dp && c->lean == 1 && c->idx_live && c->aa_sparse &&
                        c->ts == TILE2_MIN && c->d_desc != nullptr;
+    // a first token twice in a batch: the three-launch step of a single-GPU job, sparse and dense (the sharded selection,
+    // the one-launch step and forced replays keep distinct first tokens)
+    const bool share_first = c->chain_share_first && !fused && !c->forced && !dp;
+    const uint32_t sel_flags = (aa_on ? (uint32_t)PSF_AA : 0u) | (share_first ? (uint32_t)PSF_SHARE_FIRST : 0u) | ((uint32_t)c->chain_hash_kmin << 8);
     if (fused) {
         // ---- the whole step as ONE launch (k_step.hip) ----------------------------------------------------------------
         if (!c->d_step_pub) {
@@ -1326,7 +1336,7 @@ int launch_chain_step(bpe_ctx *c, uint32_t step, uint32_t zhi, bool use_index, b
         hipLaunchKernelGGL(GK(c, k_pool_sel), dim3(1 + nscan), dim3(1024), 0, c->stream, c->d_rowmax, c->d_mat,
                            c->vcap, c->d_st, stream_ref_h(c), C, c->d_dbits, c->d_lean_res, ++c->lean_tag, c->d_chain_req,
                            kcap, c->d_pool, c->d_pool_gather, hint_below, dp ? c->d_dp_ckey : (long long *)nullptr,
-                           (unsigned long long)(dp ? dp->rank : 0), c->d_pool + PL_CAP, aa_on ? 1u : 0u);
+                           (unsigned long long)(dp ? dp->rank : 0), c->d_pool + PL_CAP, sel_flags);
     LAUNCHCHK(c, "k_pool_sel");
     if (dp) {
         TRY(dp_allreduce(c, c->d_dp_ckey, DP_KEY_WORDS, BPE_DT_INT64, BPE_OP_MIN));

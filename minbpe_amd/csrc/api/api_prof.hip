@@ -42,9 +42,10 @@ int bpe_train_stats_ex(bpe_ctx *c, uint64_t *out, int n) {
         TRY(read_state(c, &stt));
         chained = stt.chain_taken;
     }
-    const uint64_t v[12] = {c->n_dense, c->n_sparse, c->n_index_builds, c->slot_T, c->n_lean, c->n_deferred,
-                            chained + c->n_chained, c->n_steps, c->n_full, (uint64_t)c->ts, c->n_fused, c->n_aa_chain};
-    for (int i = 0; i < n && i < 12; i++) out[i] = v[i];
+    const uint64_t v[13] = {c->n_dense, c->n_sparse, c->n_index_builds, c->slot_T, c->n_lean, c->n_deferred,
+                            chained + c->n_chained, c->n_steps, c->n_full, (uint64_t)c->ts, c->n_fused, c->n_aa_chain,
+                            c->n_shared_first};
+    for (int i = 0; i < n && i < 13; i++) out[i] = v[i];
     return BPE_OK;
 }
 

@@ -143,6 +143,7 @@ int dp_train_loop(bpe_ctx *c, int32_t num_merges, const DpComm &comm, int32_t *p
     uint64_t lean_at_last_defer = 0, n_chain_merges = 0;
     c->n_lean = c->n_deferred = 0;
     c->n_aa_chain = 0;
+    c->n_shared_first = 0;
     c->n_steps = c->n_full = c->n_chained = 0;
     c->rows_pending = false;
     c->sum_valid = false;

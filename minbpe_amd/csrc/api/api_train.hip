@@ -68,6 +68,7 @@ int bpe_train(bpe_ctx *c, int32_t num_merges, int32_t *pairs_out, uint64_t *coun
     c->n_steps = c->n_full = c->n_chained = 0;
     c->n_fused = 0;
     c->n_aa_chain = 0;
+    c->n_shared_first = 0;
     static const char *stamp_path = getenv("BPE_STEP_STAMPS");
     const size_t stamp_bytes = (size_t)STEP_STAMP_RING * (3 * 16 + 256 * 2) * sizeof(unsigned long long);
     if (stamp_path) {
@@ -373,6 +374,12 @@ int bpe_train(bpe_ctx *c, int32_t num_merges, int32_t *pairs_out, uint64_t *coun
                         TRY(wait_iter((int)(sr.first_iter + j)));
                         TRY(take_record((int)(sr.first_iter + j), true));  // (an a == b merge of a chain step kept the index current)
                         if (!stop && c->h_rec[sr.first_iter + j].a == c->h_rec[sr.first_iter + j].b) c->n_aa_chain++;
+                    }
+                    if (sr.k > 1 && !stop) {  // (a first token twice in the step's batch: option "chain_share_first")
+                        bool twice = false;
+                        for (uint32_t j = 1; j < sr.k && !twice; j++)
+                            for (uint32_t i = 0; i < j && !twice; i++) twice = c->h_rec[sr.first_iter + i].a == c->h_rec[sr.first_iter + j].a;
+                        if (twice) c->n_shared_first++;
                     }
                     if (sr.k) {
                         c->n_lean += sr.k;

@@ -177,7 +177,7 @@ struct DevState {
     uint32_t badj[CH_KMAX];       // delta format B, per pair of the batch: sites whose right neighbour starts a site of the SAME pair
     uint32_t bcnt[CH_KMAX];       // the pairs' counts (a batch may reach below the maximum)
     uint32_t brep;                // delta replicas per pair of this batch (CH_REP or CH_RSTRIDE)
-    uint32_t bhm, bhm_key;        // the multiplier of the batch's first-token look-up table (merge_chain_wave), found once by the selection
+    uint32_t bhm, bhm_key;        // the multiplier of the batch's pair look-up table (merge_chain_wave), found once by the selection
                                   // instead of by every workgroup of the merge pass; valid iff bhm_key == bz0 << 8 | bk
     uint32_t dp_wait;             // sharded chain steps: the selection waits for the MIN all-reduce (k_pool_sel_dp finishes it)
     // the pool (k_pool.hip): every pair that counts pool_theta or more, pool_n entries in the ctx's pool buffer

@@ -19,8 +19,9 @@
 //      reference merges next, in that order, whatever those merges create (a pair that shares a token with
 //      a merged one is not in the prefix, so whatever takes its place comes after the prefix).  (Round 6: the
 //      prefix may share SECOND tokens -- (a, b), (c, b): only a pair that could chain onto a site of the batch,
-//      x a second token or y a first one, must stay out; k_pool.hip.  First tokens stay distinct: the pass
-//      below looks a pair up by its first token.)  Their
+//      x a second token or y a first one, must stay out; k_pool.hip.  And FIRST tokens, option chain_share_first --
+//      (a, b1), (a, b2): the pass below looks a site up by its pair.  Sharded steps, k_step and forced replays keep
+//      first tokens distinct.)  Their
 //      rewrites commute (no two sites overlap): ONE pass over the candidate slots merges them all, and
 //      charges every site its pair-table delta as the sequential merges would have
 //      (delta format B per pair j: a left neighbour that ends a site of pair i < j already reads Z_i, one of
@@ -62,12 +63,22 @@ __device__ __forceinline__ int chain_match(const uint32_t *pa, const uint32_t *p
     return (w0 == INVALID_WORD) ? -1 : hit;
 }
 
-// One slot of a chain step's merge pass, by ONE WAVE: merge_ab_wave (k_slots2.hip) for K >= 2 pairs with distinct first
-// tokens, none chaining onto another (second tokens may be shared), at once.  DENSE == false: the sparse form (staged headers, global delta replicas, index live).  DENSE == true: the
+// The bucket of pair (a, b) in the merge pass's look-up table: m is the multiplier that the search varies (odd, 129 .. 255),
+// m2 follows from it.  m2 is LARGER than 256 on purpose: ids that differ by one -- the tokens a run of merges has just made
+// -- then fall at least a bucket apart, where two multipliers below 256 leave (z, y + 1) and (z + 1, y) together under
+// every m (tests/test_chain_pair_hash.py restates both functions and measures the share of key sets without a multiplier).
+__device__ __forceinline__ uint32_t chain_hash_m2(uint32_t m) { return 2u * m * m + 1u; }
+__device__ __forceinline__ uint32_t chain_pair_bucket(uint32_t a, uint32_t b, uint32_t m, uint32_t m2) {
+    return ((__umul24(a, m) + __umul24(b, m2)) >> 8) & 255u;
+}
+constexpr uint32_t CH_HASH_KMIN = 2;  // batches from this size on use the table (the host may raise it: option "chain_hash_kmin")
+
+// One slot of a chain step's merge pass, by ONE WAVE: merge_ab_wave (k_slots2.hip) for K >= 2 pairs, none chaining onto
+// another (first tokens may be shared, and second tokens), at once.  DENSE == false: the sparse form (staged headers, global delta replicas, index live).  DENSE == true: the
 // early passes, where every slot is visited and a pair has millions of sites: headers go to the other header array,
 // the delta into the workgroup's LDS tables sd (per pair p, at sd + p * CH_SD: SL[CH_DCAP] | SR[CH_DCAP] | adj |
-// ids removed; every id is below CH_DCAP), flushed by the kernel when its slots are done.  pa / pb: the pairs (LDS), pb1[p + 1] = pb[p] with
-// pb1[0] a word that matches nothing, z0: pair p becomes z0 + p.
+// ids removed; every id is below CH_DCAP), flushed by the kernel when its slots are done.  pa / pb: the pairs (LDS), ph / hm: their
+// look-up table and its multiplier (chain_hash_build; hm == 0: none, compare), z0: pair p becomes z0 + p.
 // (the tables of a DENSE chain step cover ids below CH_DCAP, not LDSD_CAP: the dense phase ends when the index comes up --
 // merge ~300 of a 1 GB stream -- and a table of 1024 ids lets eight pairs' tables fit beside the sixteen waves' staging,
 // where 1920 ids allowed four; a stream whose dense phase outlasts id 1024 goes on with the general path's single merges)
@@ -87,10 +98,10 @@ __device__ __forceinline__ void chain_slot_load(const AbArgs &A, const uint32_t 
 // (rv / hv: the slot's loads, issued by the caller -- k_merge_chain issues the NEXT slot's before it works on this one)
 template <bool DENSE, bool THROUGH = false>
 __device__ __forceinline__ void merge_chain_wave(uint32_t *__restrict__ out, uint32_t *__restrict__ sd, const uint32_t t, const AbArgs &A,
-                                                 const uint32_t *pa, const uint32_t *pb, const uint32_t *pb1,
+                                                 const uint32_t *pa, const uint32_t *pb,
                                                  const uint32_t K, const uint32_t z0, const uint32_t brep,
                                                  uint4 (&rv)[MJ], const uint4 hv,
-                                                 const uint32_t *ph = nullptr, const uint32_t hm = 0,
+                                                 const uint2 *ph = nullptr, const uint32_t hm = 0,
                                                  const uint32_t tl_in = 0xFFFFFFFFu) {
     const int lane = lane_id();
     // (tl_in: the caller read st->tlive once -- the kernel stores to *st, so a load here is repeated for every slot, a
@@ -162,55 +173,53 @@ __device__ __forceinline__ void merge_chain_wave(uint32_t *__restrict__ out, uin
         rb[j] = 0;
         jc[j] = 0;
     }
-    // Two stages, so that the work per word does not grow with K twice over (four waves share a SIMD: with
-    // every word compared against every pair the pass was bound by instruction issue, not by the slot's
-    // latency): which pair's FIRST token is this word (K compares), then ONE compare of the next word with that
-    // pair's second token, fetched from LDS by pair number (pb1[0] matches nothing: no pair).
+    // ONE look-up per position, keyed by the PAIR (word, next word): a batch may hold several pairs with one first token
+    // -- (a, b1), (a, b2): their sites never overlap and neither merge moves the other's count --, so the first token alone
+    // does not name the pair.  ph is a 256-entry table of 8-byte entries in LDS, {a << 8 | pair number + 1, b}, read with one
+    // 64-bit load; chain_pair_bucket is free of collisions among the batch's pairs (chain_hash_build).  The chunk-start flag
+    // of the next word stays in the comparison (no pair spans chunks); INVALID_WORD's id matches no entry.  hm == 0 (no
+    // multiplier found, or the selection was told not to look): every position is compared with every pair, both tokens.
     uint32_t s = 0;  // carry: my first word is the second word of a site that starts at the previous slot's last word
-    uint32_t ia[MJ];  // a byte per word: the pair whose first token it is, + 1 (tokens are distinct: at most one)
+    uint32_t ip = 0;  // ... and that site's pair number + 1
+    uint32_t nxw[MJ];  // the word after my four
 #pragma unroll
-    for (int j = 0; j < MJ; j++) ia[j] = 0;
-    uint32_t ip = 0;
+    for (int j = 0; j < MJ; j++) {
+        const uint32_t up = (j < MJ - 1) ? lane_first(x[(j + 1) % MJ][0]) : tail[0];
+        nxw[j] = lane_next(x[j][0], up);
+    }
     if (hm) {
-        // a batch of five pairs or more: ONE look-up per word instead of K compares -- ph is a 256-entry table in LDS,
-        // (id * hm >> 8) & 255 is free of collisions among the batch's first tokens (chain_hash_build), an entry is
-        // id << 8 | pair number + 1
-        auto code = [&](uint32_t w) -> uint32_t {
+        const uint32_t hm2 = chain_hash_m2(hm);
+        auto code = [&](uint32_t w, uint32_t nx) -> uint32_t {
             const uint32_t id = w & IDMASK;
-            const uint32_t e = ph[(__umul24(id, hm) >> 8) & 255u];
-            return (e >> 8) == id ? (e & 255u) : 0u;
+            const uint2 e = ph[chain_pair_bucket(id, nx & IDMASK, hm, hm2)];
+            return ((e.x >> 8) == id && e.y == (nx & NWMASK)) ? (e.x & 255u) : 0u;
         };
 #pragma unroll
         for (int j = 0; j < MJ; j++) {
 #pragma unroll
-            for (int k = 0; k < 4; k++) ia[j] |= code(x[j][k]) << (8 * k);
+            for (int k = 0; k < 4; k++) jc[j] |= code(x[j][k], (k < 3) ? x[j][(k + 1) & 3] : nxw[j]) << (8 * k);
         }
-        ip = code(prev1);
+        ip = code(prev1, first);
     } else {
         for (uint32_t p = 0; p < K; p++) {
-            const uint32_t a = pa[p];
+            const uint32_t a = pa[p], b = pb[p];
 #pragma unroll
             for (int j = 0; j < MJ; j++) {
 #pragma unroll
-                for (int k = 0; k < 4; k++) ia[j] |= ((x[j][k] & IDMASK) == a) ? (p + 1u) << (8 * k) : 0u;
+                for (int k = 0; k < 4; k++) {
+                    const uint32_t nxt = (k < 3) ? x[j][(k + 1) & 3] : nxw[j];
+                    jc[j] |= (((x[j][k] & IDMASK) == a) & ((nxt & NWMASK) == b)) ? (p + 1u) << (8 * k) : 0u;
+                }
             }
-            ip = ((prev1 & IDMASK) == a) ? p + 1u : ip;
+            ip = (((prev1 & IDMASK) == a) & ((first & NWMASK) == b)) ? p + 1u : ip;
         }
     }
 #pragma unroll
     for (int j = 0; j < MJ; j++) {
-        const uint32_t up = (j < MJ - 1) ? lane_first(x[(j + 1) % MJ][0]) : tail[0];
-        const uint32_t nxw = lane_next(x[j][0], up);
 #pragma unroll
-        for (int k = 0; k < 4; k++) {
-            const uint32_t nxt = (k < 3) ? x[j][k + 1] : nxw;
-            const uint32_t i = (ia[j] >> (8 * k)) & 255u;
-            const uint32_t m = (uint32_t)((nxt & NWMASK) == pb1[i]);
-            rb[j] |= m << k;
-            jc[j] |= (m ? i : 0u) << (8 * k);
-        }
+        for (int k = 0; k < 4; k++) rb[j] |= (uint32_t)(((jc[j] >> (8 * k)) & 255u) != 0u) << k;
     }
-    s = (uint32_t)((prev1 != INVALID_WORD) & ((first & NWMASK) == pb1[ip]));
+    s = (uint32_t)((prev1 != INVALID_WORD) & (ip != 0u));
 #pragma unroll
     for (int j = 0; j < MJ; j++) {
         const int nb = (int)len - (j * 256 + lane * 4);
@@ -569,22 +578,24 @@ __device__ __forceinline__ void merge_aa_wave(uint32_t *scr, const uint32_t t, c
     __builtin_amdgcn_wave_barrier();
 }
 
-// The look-up table of a batch's first tokens (merge_chain_wave): one wave looks for a multiplier m (odd, 129 .. 255) under
-// which no two of the K tokens fall into the same of the 256 buckets (K = 15: two in three multipliers do, K = 31: one in
-// six -- none of the 64 about once in 10^5 batches); returns it to every lane (0: none found, or a batch too small to pay
-// -- the pass compares).  Two multipliers per round, one per half of the wave, a token per lane: every lane writes its
+// The look-up table of a batch's pairs (merge_chain_wave): one wave looks for a multiplier m (odd, 129 .. 255) under
+// which no two of the K pairs fall into the same of the 256 buckets (chain_pair_bucket; K = 15: two in three multipliers do,
+// K = 31: one in six); returns it to every lane (0: none found, or a batch smaller than kmin -- the pass compares).  Two
+// multipliers per round, one per half of the wave, a pair per lane: every lane writes its
 // number into its bucket of the half's table and reads the bucket back -- of two lanes in one bucket at least one reads
 // the other's number (no clearing: a lane only reads a bucket it has just written).  A round is two LDS accesses whatever
-// K is, and a small batch is done after one (K^2 / 2 compares per multiplier before: too many at K = 31).
+// K is, and a small batch is done after one.
 // tab: 512 words of LDS scratch.  All 64 lanes of the wave call.
-__device__ __forceinline__ uint32_t chain_hash_find(const uint32_t *pa, uint32_t K, uint32_t *tab) {
-    if (K < 5) return 0u;
+__device__ __forceinline__ uint32_t chain_hash_find(const uint32_t *pa, const uint32_t *pb, uint32_t K, uint32_t *tab,
+                                                    uint32_t kmin = CH_HASH_KMIN) {
+    if (K < kmin) return 0u;
     const uint32_t lane = (uint32_t)lane_id(), half = lane >> 5, l = lane & 31u;
     const bool in = l < K;
-    const uint32_t a = in ? pa[l] : 0u;
+    const uint32_t a = in ? pa[l] : 0u, b = in ? pb[l] : 0u;
     volatile uint32_t *t = tab + half * 256u;
     for (uint32_t m = 129u; m < 256u; m += 4u) {
-        const uint32_t h = (__umul24(a, m + 2u * half) >> 8) & 255u;
+        const uint32_t mm = m + 2u * half;
+        const uint32_t h = chain_pair_bucket(a, b, mm, chain_hash_m2(mm));
         if (in) t[h] = l;
         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
         __builtin_amdgcn_wave_barrier();
@@ -596,16 +607,17 @@ __device__ __forceinline__ uint32_t chain_hash_find(const uint32_t *pa, uint32_t
     }
     return 0u;
 }
-// (pre_ok: the selection already found the multiplier, pre_hm -- k_pool.hip: pool_finish; DevState::bhm)
-__device__ __forceinline__ uint32_t chain_hash_build(uint32_t *s_ph, uint32_t *s_hm, uint32_t *s_hs, const uint32_t *s_pa, uint32_t K,
-                                                     bool pre_ok = false, uint32_t pre_hm = 0) {
-    if (threadIdx.x < 256) s_ph[threadIdx.x] = 0xFFFFFFFFu;
+// (pre_ok: the selection already found the multiplier, pre_hm -- k_pool.hip: pool_finish; DevState::bhm.  s_hs may be null
+// where pre_ok always holds.)
+__device__ __forceinline__ uint32_t chain_hash_build(uint2 *s_ph, uint32_t *s_hm, uint32_t *s_hs, const uint32_t *s_pa,
+                                                     const uint32_t *s_pb, uint32_t K, bool pre_ok = false, uint32_t pre_hm = 0) {
+    if (threadIdx.x < 256) s_ph[threadIdx.x] = make_uint2(0xFFFFFFFFu, 0xFFFFFFFFu);  // (matches no id, no masked word)
     uint32_t hm = pre_hm;
     if (!pre_ok) {  // (uniform)
         if (threadIdx.x == 0) *s_hm = 0;
         __syncthreads();
         if (wave_id() == 0) {
-            const uint32_t f = chain_hash_find(s_pa, K, s_hs);
+            const uint32_t f = chain_hash_find(s_pa, s_pb, K, s_hs);
             if (lane_id() == 0) *s_hm = f;
         }
         __syncthreads();
@@ -613,7 +625,9 @@ __device__ __forceinline__ uint32_t chain_hash_build(uint32_t *s_ph, uint32_t *s
     } else {
         __syncthreads();
     }
-    if (hm && threadIdx.x < K) s_ph[(__umul24(s_pa[threadIdx.x], hm) >> 8) & 255u] = (s_pa[threadIdx.x] << 8) | (threadIdx.x + 1u);
+    if (hm && threadIdx.x < K)
+        s_ph[chain_pair_bucket(s_pa[threadIdx.x], s_pb[threadIdx.x], hm, chain_hash_m2(hm))] =
+            make_uint2((s_pa[threadIdx.x] << 8) | (threadIdx.x + 1u), s_pb[threadIdx.x]);
     __syncthreads();
     return hm;
 }
@@ -626,11 +640,12 @@ struct MergeLds {
     alignas(16) uint32_t s_out[LEAN_MT / 64][TILE2];
     uint32_t s_list[LEAN_SUB * 32];
     uint32_t s_tot[2];
-    uint32_t s_pa[CH_KMAX], s_pb[CH_KMAX], s_pb1[CH_KMAX + 1];
-    uint32_t s_ph[256], s_hm;
+    uint32_t s_pa[CH_KMAX], s_pb[CH_KMAX];
+    alignas(8) uint2 s_ph[256];  // (the pairs' look-up table: chain_hash_build)
+    uint32_t s_hm;
     uint32_t s_hs[512];  // (chain_hash_find's scratch)
 };
-// (s_pa / s_pb / s_pb1 are filled and a barrier has passed; every thread of the workgroup calls; THROUGH: k_step -- the
+// (s_pa / s_pb are filled and a barrier has passed; every thread of the workgroup calls; THROUGH: k_step -- the
 // staged headers are committed by other workgroups of the same launch)
 template <bool THROUGH = false>
 __device__ __forceinline__ void merge_chain_body(const AbArgs &A, const uint32_t *__restrict__ idx_dirty, uint32_t use_index,
@@ -647,9 +662,8 @@ __device__ __forceinline__ void merge_chain_body(const AbArgs &A, const uint32_t
     auto &s_tot = L.s_tot;
     auto &s_pa = L.s_pa;
     auto &s_pb = L.s_pb;
-    auto &s_pb1 = L.s_pb1;
-    const uint32_t hm = chain_hash_build(L.s_ph, &L.s_hm, L.s_hs, s_pa, K, pre_ok, pre_hm);
-    const uint32_t *s_ph = L.s_ph;
+    const uint32_t hm = chain_hash_build(L.s_ph, &L.s_hm, L.s_hs, s_pa, s_pb, K, pre_ok, pre_hm);
+    const uint2 *s_ph = L.s_ph;
     // (have_st: the caller fetched the state words this pass needs in one round trip with the batch)
     const uint32_t Tl = min(A.T, have_st ? tlive_in : st->tlive);
     const uint32_t gap = have_st ? gap_in : st->gap;
@@ -674,7 +688,7 @@ __device__ __forceinline__ void merge_chain_body(const AbArgs &A, const uint32_t
         } else {
             uint4 rv[MJ], hv;
             chain_slot_load(A, t, rv, hv);
-            merge_chain_wave<false, THROUGH>(s_out[wave_id()], nullptr, t, A, s_pa, s_pb, s_pb1, K, z0, brep, rv, hv, s_ph, hm, Tl);
+            merge_chain_wave<false, THROUGH>(s_out[wave_id()], nullptr, t, A, s_pa, s_pb, K, z0, brep, rv, hv, s_ph, hm, Tl);
         }
     };
     if (!(use_index & 1u) || gap != 0) {  // short slots about: visit everything
@@ -739,7 +753,7 @@ __device__ __forceinline__ void merge_chain_body(const AbArgs &A, const uint32_t
             for (; i < n; i += NWV) {
                 const bool more = i + NWV < n;
                 if (more) chain_slot_load(A, s_list[i + NWV], nrv, nhv);
-                merge_chain_wave<false, THROUGH>(s_out[wave_id()], nullptr, s_list[i], A, s_pa, s_pb, s_pb1, K, z0, brep, rv, hv, s_ph, hm, Tl);
+                merge_chain_wave<false, THROUGH>(s_out[wave_id()], nullptr, s_list[i], A, s_pa, s_pb, K, z0, brep, rv, hv, s_ph, hm, Tl);
                 if (more) {
 #pragma unroll
                     for (int j = 0; j < MJ; j++) rv[j] = nrv[j];
@@ -797,8 +811,6 @@ k_merge_chain(AbArgs A, const uint32_t *__restrict__ idx_dirty, uint32_t use_ind
     if (threadIdx.x < CH_KMAX) {
         L.s_pa[threadIdx.x] = threadIdx.x < K ? s_w[threadIdx.x] : 0xFFFFFFFFu;
         L.s_pb[threadIdx.x] = threadIdx.x < K ? s_w[SW_BB + threadIdx.x] : 0xFFFFFFFFu;
-        L.s_pb1[threadIdx.x + 1] = threadIdx.x < K ? s_w[SW_BB + threadIdx.x] : 0xFFFFFFFFu;
-        if (threadIdx.x == 0) L.s_pb1[0] = 0xFFFFFFFFu;  // (a masked word has its weight bits clear: never equal)
     }
     __syncthreads();
     // (a == b heads the batch although the host left the a == b pass off: the selection and this launch disagree)
@@ -816,13 +828,13 @@ k_merge_chain(AbArgs A, const uint32_t *__restrict__ idx_dirty, uint32_t use_ind
 // A batch of K pairs costs ONE sweep over the stream instead of K.  One 1024-thread workgroup per CU, wave w of the
 // grid takes slots w, w + waves, ...; every slot's header is written to the other header array (the host flips the
 // arrays after every dense step -- a step that merges nothing copies the headers across, so that the flip stands).
-constexpr int CH_KDENSE = 6;  // most pairs of a dense step's batch: their LDS tables must fit next to the staging (8 pairs measured no faster than 6; the first-token look-up table of the sparse pass measured no faster than K compares here)
+constexpr int CH_KDENSE = 6;  // most pairs of a dense step's batch: their LDS tables must fit next to the staging (8 pairs measured no faster than 6; the look-up table of the sparse pass measured no faster than K compares here when it was keyed by the first token, and the pair-keyed one costs the 256-id geometry a wave of occupancy in the compiler's report: the dense pass compares)
 static_assert((LEAN_MT / 64) * TILE2 * 4 + CH_KDENSE * (int)CH_SD * 4 + 256 <= 160 * 1024, "dense chain pass: LDS");
 __global__ void __launch_bounds__(LEAN_MT)
 k_merge_chain_dense(AbArgs A, uint32_t *__restrict__ dbits) {
     __shared__ __attribute__((aligned(16))) uint32_t s_out[LEAN_MT / 64][TILE2];
     __shared__ uint32_t s_sd[CH_KDENSE * CH_SD];
-    __shared__ uint32_t s_pa[CH_KMAX], s_pb[CH_KMAX], s_pb1[CH_KMAX + 1];
+    __shared__ uint32_t s_pa[CH_KMAX], s_pb[CH_KMAX];
     DevState *st = A.st;
     const uint32_t ran = st->sel_ran;
     if (blockIdx.x == 0 && ran) {
@@ -844,8 +856,6 @@ k_merge_chain_dense(AbArgs A, uint32_t *__restrict__ dbits) {
     if (threadIdx.x < CH_KMAX) {
         s_pa[threadIdx.x] = threadIdx.x < K ? (uint32_t)st->ba[threadIdx.x] : 0xFFFFFFFFu;
         s_pb[threadIdx.x] = threadIdx.x < K ? (uint32_t)st->bb[threadIdx.x] : 0xFFFFFFFFu;
-        s_pb1[threadIdx.x + 1] = threadIdx.x < K ? (uint32_t)st->bb[threadIdx.x] : 0xFFFFFFFFu;
-        if (threadIdx.x == 0) s_pb1[0] = 0xFFFFFFFFu;
     }
     for (uint32_t i = threadIdx.x; i < K * CH_SD; i += LEAN_MT) s_sd[i] = 0;
     __syncthreads();
@@ -856,7 +866,7 @@ k_merge_chain_dense(AbArgs A, uint32_t *__restrict__ dbits) {
     {
         uint4 rv[MJ], hv;
         chain_slot_load(A, t, rv, hv);
-        merge_chain_wave<true>(s_out[wave_id()], s_sd, t, A, s_pa, s_pb, s_pb1, K, z0, (uint32_t)CH_RSTRIDE, rv, hv, nullptr, 0, Tl);
+        merge_chain_wave<true>(s_out[wave_id()], s_sd, t, A, s_pa, s_pb, K, z0, (uint32_t)CH_RSTRIDE, rv, hv, nullptr, 0, Tl);
     }
     __syncthreads();
     // flush: the tables of pair p into one of its CH_RSTRIDE replica blocks
@@ -1349,10 +1359,13 @@ k_forced_sel(DevState *st, const int32_t *__restrict__ pairs, const uint32_t *__
     const uint32_t K = bb ? min(kcap, (uint32_t)__ffsll((long long)bb) - 1u) : kcap;
     const uint32_t c = lane < K ? mat[(size_t)a * stride + b] : 0u;
     const uint32_t cmax = wave_umax_dpp(c);
-    __shared__ uint32_t s_pa[CH_KMAX], s_hs[512];
-    if (lane < CH_KMAX) s_pa[lane] = a;
+    __shared__ uint32_t s_pa[CH_KMAX], s_pb[CH_KMAX], s_hs[512];
+    if (lane < CH_KMAX) {
+        s_pa[lane] = a;
+        s_pb[lane] = b;
+    }
     __syncthreads();
-    const uint32_t hm = chain_hash_find(s_pa, K, s_hs);
+    const uint32_t hm = chain_hash_find(s_pa, s_pb, K, s_hs);
     if (lane == 0) {
         st_agent(&st->adj, 0u);
         st->count = c;

@@ -14,8 +14,10 @@
 //   a step      maintain (below) -> sort by (count descending, key) -> the levels the walk can reach that hold several
 //               entries and are not CLEAN (all entries of one epoch) are located afresh through the index, all at once
 //               -> the batch = the longest prefix with a != b in which no pair could chain onto a site of another -- (x, y)
-//               with x a second token or y a first token of a pair before it -- and no first token comes twice; a SECOND
-//               token may (round 6: sites of (a, b) and (c, b) never overlap, neither merge moves the other's count, and
+//               with x a second token or y a first token of a pair before it; a SECOND token may come twice, and a FIRST
+//               one where the merge pass finds a site by its pair (share_first: the three-launch step of a single-GPU
+//               job; elsewhere no first token comes twice) (round 6: sites of (a, b) and (c, b) never overlap -- nor do
+//               those of (a, b1) and (a, b2) --, neither merge moves the other's count, and
 //               what a merge lowers or creates -- (L, a), (b, R) and their heirs -- chains onto the batch and stops the walk
 //               where it stands; tests/test_level_model.py: walking the levels from the top, inside a level in order of first
 //               occurrence, under this rule is what the reference merges) -> the rest of the entries is the pool of the next step;
@@ -23,7 +25,8 @@
 //               one (-> Zy) has its occurrences spread over (x, y), (Zx, y), (x, Zy), (Zx, Zy): each of the four that
 //               counts >= theta in the updated table is an entry; the one whose count EQUALS the entry's old count
 //               took over every occurrence and stands where the entry stood (it inherits the key), the others have no
-//               order.  (Several batch pairs p may end in x: a variant (Z_p, y), (Z_p, Zy) for each.)  Every other entry is
+//               order.  (Several batch pairs p may end in x, several q may start with y: the variants are
+//               ({x} + {Z_p}) x ({y} + {Z_q}).)  Every other entry is
 //               untouched.  No pair from outside the pool can reach theta: a created pair
 //               (L, Z) / (Z, R) / (Zi, Zj) counts at most what (L, a) / (b, R) / (bi, aj) counted before;
 //   rebuild     pool (nearly) empty: the flagged rows are re-scanned (workgroups 1..), the deciding workgroup picks a new
@@ -152,7 +155,7 @@ __device__ __forceinline__ void pool_levels_dirty(const unsigned long long *key,
     __syncthreads();
 }
 // The end of a selection, once the keys are what they are going to be (b_*: the pool sorted by count, s_ls / s_le its
-// level bounds): the order inside every level, the batch -- the longest prefix with a != b, no pair chaining onto another, no first token twice, every level
+// level bounds): the order inside every level, the batch -- the longest prefix with a != b, no pair chaining onto another, no first token twice unless share_first, every level
 // it enters in a known order --, the step's state, and the rest of the entries as the next step's pool.  Every thread of
 // the deciding workgroup calls (blockDim.x >= PL_CAP).
 __device__ __forceinline__ void pool_finish(DevState *st, PoolEnt *__restrict__ pool, const uint32_t *b_xy, const uint32_t *b_c,
@@ -160,7 +163,8 @@ __device__ __forceinline__ void pool_finish(DevState *st, PoolEnt *__restrict__ 
                                             unsigned long long *a_key, const uint32_t *s_ls, const uint32_t *s_le,
                                             uint32_t *s_dirty, uint32_t *s_clash, uint32_t *s_k, uint32_t *s_unt, uint32_t n,
                                             uint32_t kmax, uint32_t iter, uint32_t theta, unsigned long long epoch, bool rebuilt,
-                                            uint32_t hint_below, int ksh, PoolScratch &X, const bool aa_ok = false) {
+                                            uint32_t hint_below, int ksh, PoolScratch &X, const bool aa_ok = false,
+                                            const bool share_first = false, const uint32_t hash_kmin = CH_HASH_KMIN) {
     const uint32_t tid = threadIdx.x;
     const uint32_t nwalk = min(n, kmax);
     // ---- the order inside every level: by key (a level whose keys are not of one epoch stays without an order) ----------
@@ -200,7 +204,7 @@ __device__ __forceinline__ void pool_finish(DevState *st, PoolEnt *__restrict__ 
         s_dirty[r] = X.dl[lo];
     }
     __syncthreads();
-    // ---- the batch: the longest prefix with a != b, no chain, no first token twice, every level entered in a known order ----
+    // ---- the batch: the longest prefix with a != b, no chain, (no first token twice,) every level entered in a known order ----
     // (a thread per entry i and earlier entry j -- nwalk <= CH_KSWEEP < 32: 32 nwalk of them, one round of a 1024-thread
     // selection; a wave that let entry i walk through every j < i took 30 dependent turns for a walk of 31)
     for (uint32_t q2 = tid; q2 < 32u * nwalk; q2 += blockDim.x) {
@@ -216,8 +220,10 @@ __device__ __forceinline__ void pool_finish(DevState *st, PoolEnt *__restrict__ 
             if (j == 0 && xj == yj) bad = true;  // (the batch of one: nothing joins it)
             // (a SECOND token may be shared: sites of (a, b) and (c, b) never overlap and neither merge moves the
             // other's count -- only a pair that could chain onto a site of the batch, x a second token or y a first
-            // one, stops the walk; first tokens stay distinct: the merge pass looks a pair up by its first token)
-            bad |= (xj == x) | (xj == y) | (yj == x);
+            // one, stops the walk.  share_first: a FIRST token may be shared too, for the same reason -- (a, b1) and
+            // (a, b2) with b1 == a or b2 == a are chains, which the test excludes; the merge pass looks a site up by
+            // its pair.  Off for the selections whose rule stays the earlier one: sharded steps, k_step.)
+            bad |= ((xj == x) & !share_first) | (xj == y) | (yj == x);
         }
         if (bad) atomicOr(&X.bad, 1u << i);
     }
@@ -251,7 +257,10 @@ __device__ __forceinline__ void pool_finish(DevState *st, PoolEnt *__restrict__ 
         }
     }
     if (K == 0) return;
-    if (tid < K) X.rank[tid] = a_xy[tid] >> 16;  // (the batch's first tokens, for chain_hash_find below)
+    if (tid < K) {  // (the batch's pairs, for chain_hash_find below)
+        X.rank[tid] = a_xy[tid] >> 16;
+        X.rank[CH_KMAX + tid] = a_xy[tid] & 0xFFFFu;
+    }
     __syncthreads();
     if (tid < 64) {  // the batch itself, a pair per lane
         uint32_t c = 0;
@@ -263,9 +272,9 @@ __device__ __forceinline__ void pool_finish(DevState *st, PoolEnt *__restrict__ 
             st->bcnt[tid] = c;
         }
         const uint32_t cmax = wave_umax_dpp(c);
-        // the multiplier of the merge pass's first-token look-up table, found here once (chain_hash_find, k_chain.hip)
+        // the multiplier of the merge pass's pair look-up table, found here once (chain_hash_find, k_chain.hip)
         // instead of by every workgroup of the pass; the key says which batch it belongs to
-        const uint32_t hm = chain_hash_find(reinterpret_cast<const uint32_t *>(X.rank), K, X.rank + 256);
+        const uint32_t hm = chain_hash_find(X.rank, X.rank + CH_KMAX, K, X.rank + 256, hash_kmin);
         if (tid == 0) {
             st->brep = cmax > CH_REP_COUNT ? (uint32_t)CH_RSTRIDE : (uint32_t)CH_REP;
             st->bhm = hm;
@@ -304,6 +313,7 @@ __device__ __forceinline__ void pool_finish(DevState *st, PoolEnt *__restrict__ 
 }
 
 // The LDS of a selection (one struct, so that k_step can overlay it with its merge pass's).
+enum : uint32_t { PSF_AA = 1u, PSF_SHARE_FIRST = 2u };  // (pool_sel_body's flags)
 struct PoolLds {
     unsigned long long s_red[32];
     uint32_t s_words[DBITS_WORDS], s_pref[DBITS_WORDS + 1];
@@ -326,7 +336,11 @@ pool_sel_body(uint32_t *__restrict__ rowmax, uint32_t *__restrict__ mat, uint32_
               const CandArgs &C, uint32_t *__restrict__ dbits, unsigned long long *__restrict__ res, uint32_t tag,
               unsigned long long *__restrict__ req, uint32_t kcap, PoolEnt *__restrict__ pool, uint32_t *__restrict__ gather,
               uint32_t hint_below, long long *__restrict__ dpkey, unsigned long long dprank, PoolEnt *__restrict__ mid,
-              PoolLds &L, const uint32_t blk, const uint32_t nblk, unsigned long long *dbg = nullptr, const bool aa_ok = false) {
+              PoolLds &L, const uint32_t blk, const uint32_t nblk, unsigned long long *dbg = nullptr, const uint32_t flags = 0) {
+    // flags: PSF_AA = the merge pass of this step does a == b at the head of the order itself, PSF_SHARE_FIRST = a batch may
+    // hold a first token twice, bits 8.. = the smallest batch whose pass uses the pair look-up table (0: CH_HASH_KMIN)
+    const bool aa_ok = (flags & PSF_AA) != 0, share_first = (flags & PSF_SHARE_FIRST) != 0;
+    const uint32_t hash_kmin = (flags >> 8) ? (flags >> 8) : CH_HASH_KMIN;
     auto dstamp = [&](int i) {  // (debug, BPE_STEP_STAMPS: where a selection's time goes)
         if (dbg && threadIdx.x == 0 && blk == 0) dbg[i] = wall_clock64();
     };
@@ -480,19 +494,20 @@ pool_sel_body(uint32_t *__restrict__ rowmax, uint32_t *__restrict__ mat, uint32_
     // ---- maintain: what the last batch made of my entry ------------------------------------------------------------
     uint32_t vx[4] = {0, 0, 0, 0}, vy[4] = {0, 0, 0, 0}, cv[4] = {0, 0, 0, 0}, keepm = 0, ec = 0;
     unsigned long long ekey = 0;
-    // (an entry (x, y) whose x is the second token of SEVERAL batch pairs p has a variant (Z_p, y) -- and (Z_p, Zy) -- for
-    // each of them: counted here, looked up again when they are written; rare, and the four-variant path stays as it was)
-    uint32_t mxm = 0, nmulti = 0;
+    // (an entry (x, y) whose x is the second token of SEVERAL batch pairs p, or whose y is the first token of several batch
+    // pairs q, has the variants ({x} + {Z_p}) x ({y} + {Z_q}): counted here, looked up again when they are written; rare,
+    // and the four-variant path stays as it was.  Bit 31 of a mask stands for the token itself: a batch has 31 pairs at most.)
+    uint32_t mxm = 0, mym = 0, nmulti = 0;
     bool multi = false;
     auto multi_variants = [&](auto &&emit) {
         const uint32_t zp = s_sw[PW_BZ0];
         const uint32_t x = vx[0], y = vy[0];
-        const bool hy = vy[2] != y;
         for (uint32_t m = mxm | 0x80000000u; m; m &= m - 1u) {
             const uint32_t p = (uint32_t)__ffs((int)m) - 1u;
             const uint32_t lx = p == 31u ? x : zp + p;
-            for (uint32_t r = 0; r < (hy ? 2u : 1u); r++) {
-                const uint32_t ry = r ? vy[2] : y;
+            for (uint32_t m2 = mym | 0x80000000u; m2; m2 &= m2 - 1u) {
+                const uint32_t q = (uint32_t)__ffs((int)m2) - 1u;
+                const uint32_t ry = q == 31u ? y : zp + q;
                 const uint32_t c = mat[(size_t)lx * stride + ry];
                 if (c >= theta) emit(lx, ry, c);
             }
@@ -510,9 +525,13 @@ pool_sel_body(uint32_t *__restrict__ rowmax, uint32_t *__restrict__ mat, uint32_
                 zx = (int32_t)(zp + p);
                 mxm |= 1u << p;
             }
-            if (s_sw[p] == y) zy = (int32_t)(zp + p);
+            if (s_sw[p] == y) {
+                zy = (int32_t)(zp + p);
+                mym |= 1u << p;
+            }
         }
-        multi = (mxm & (mxm - 1u)) != 0;  // several pairs of the batch end in x (a batch may share second tokens)
+        // several pairs of the batch end in x, or start with y (a batch may share second tokens, and first ones)
+        multi = ((mxm & (mxm - 1u)) | (mym & (mym - 1u))) != 0;
         vx[0] = vx[2] = x;
         vx[1] = vx[3] = zx >= 0 ? (uint32_t)zx : x;
         vy[0] = vy[1] = y;
@@ -566,7 +585,7 @@ pool_sel_body(uint32_t *__restrict__ rowmax, uint32_t *__restrict__ mat, uint32_
     dstamp(9);
     uint32_t n1 = 0;
     if (n0) for (uint32_t w = 0; w < PL_CAP / 64; w++) n1 += s_wtot[w];
-    if (n1 > PL_GATHER) n1 = 0;  // (more variants than the arrays hold -- shared second tokens only: the pool is gathered afresh)
+    if (n1 > PL_GATHER) n1 = 0;  // (more variants than the arrays hold -- shared tokens only: the pool is gathered afresh)
     bool rebuilt = false;
     // (a hinted launch -- the scanning workgroups stayed -- whose pool could not fill a batch any more gathers a fresh,
     // deeper one instead of merging the last few entries in small batches: the old entries are in it, without their keys)
@@ -780,7 +799,7 @@ pool_sel_body(uint32_t *__restrict__ rowmax, uint32_t *__restrict__ mat, uint32_
             const uint32_t x = b_xy[t] >> 16, y = b_xy[t] & 0xFFFFu;
             for (uint32_t i = tid / PL_CAP; i < nwalk; i += blockDim.x / PL_CAP) {
                 const uint32_t xi = b_xy[i] >> 16, yi = b_xy[i] & 0xFFFFu;
-                if (t != i && t < s_le[i] && ((xi == x) | (xi == y) | (yi == x))) s_clash[i] = 1;
+                if (t != i && t < s_le[i] && (((xi == x) & !share_first) | (xi == y) | (yi == x))) s_clash[i] = 1;
             }
             if (tid < nwalk && x == y) s_clash[tid] = 1;
         }
@@ -870,7 +889,7 @@ pool_sel_body(uint32_t *__restrict__ rowmax, uint32_t *__restrict__ mat, uint32_
     }
     dstamp(13);
     pool_finish(st, pool, b_xy, b_c, b_key, a_xy, a_c, a_key, s_ls, s_le, s_dirty, s_clash, &s_k, &s_unt, n, kmax, iter, theta,
-                epoch, rebuilt, hint_below, PL_KSH, X, aa_ok);
+                epoch, rebuilt, hint_below, PL_KSH, X, aa_ok, share_first, hash_kmin);
     dstamp(14);
 }
 
@@ -879,10 +898,10 @@ k_pool_sel(uint32_t *__restrict__ rowmax, uint32_t *__restrict__ mat, uint32_t s
            CandArgs C, uint32_t *__restrict__ dbits, unsigned long long *__restrict__ res, uint32_t tag,
            unsigned long long *__restrict__ req, uint32_t kcap, PoolEnt *__restrict__ pool, uint32_t *__restrict__ gather,
            uint32_t hint_below, long long *__restrict__ dpkey, unsigned long long dprank, PoolEnt *__restrict__ mid,
-           uint32_t aa_ok) {
+           uint32_t flags) {
     __shared__ PoolLds L;
     pool_sel_body(rowmax, mat, stride, st, ref, C, dbits, res, tag, req, kcap, pool, gather, hint_below, dpkey, dprank, mid, L,
-                  blockIdx.x, gridDim.x, nullptr, aa_ok != 0);
+                  blockIdx.x, gridDim.x, nullptr, flags);
 }
 
 // k_pool_sel_dp: the second half of a sharded selection, after the MIN all-reduce of the first occurrences (one workgroup

@@ -141,8 +141,6 @@ k_step(StepArgs S) {
             const uint32_t w = tid < K ? s_b[2 + tid] : 0u;
             L.s_pa[tid] = tid < K ? (w >> 16) : 0xFFFFFFFFu;
             L.s_pb[tid] = tid < K ? (w & 0xFFFFu) : 0xFFFFFFFFu;
-            L.s_pb1[tid + 1] = tid < K ? (w & 0xFFFFu) : 0xFFFFFFFFu;
-            if (tid == 0) L.s_pb1[0] = 0xFFFFFFFFu;  // (a masked word has its weight bits clear: never equal)
         }
         __syncthreads();
         merge_chain_body<true>(S.A, S.idx_dirty, S.use_index, L, K, z0, brep, blockIdx.x, S.gm, blockIdx.x == 0 ? nullptr : dbg);

@@ -23,7 +23,10 @@ against the oracle's sequence, and at every step boundary evaluates three batch 
            pins it against the reference semantics -- so "free" is the rule to build, "tied" a weaker form of it
   free_s2, free_rx   (round 6, RULES=free,free_s2,free_rx) "free" with a weaker clash rule: only a pair that could OVERLAP a site
            of the batch stops the walk -- (x, y) with x a second token or y a first token of the batch (a chain a b d), and
-           a == b; free_s2 still keeps first tokens distinct (the merge pass looks a pair up by its first token)
+           a == b; free_s2 still keeps first tokens distinct (the merge pass looked a pair up by its first token); free_rx is
+           the rule of option chain_share_first
+  <rule>_d6   any rule with the cap of a DENSE chain step, six pairs (CH_KDENSE), for the steps that start before merge
+           DENSE_UNTIL (environment, default 300: about where the index comes up in the headline run)
 
     python tools/level_model.py seq.json [cap ...] > profiles/r4_level_model.json     (seq.json: tools/batch_model.py --make)
 """
@@ -210,6 +213,7 @@ def main():
     rules = tuple(os.environ.get("RULES", "engine,tied,free,free1,engine+list,free+list,free1+list").split(","))
     res = {f"{r}_cap{cap}": {"steps": 0, "next": 0, "by_phase": {}, "list": None, "full": 0} for r in rules for cap in caps}
     edges = [0, 300, 1000, 2000, 4000, 8000, 16000, 24000, M]
+    dense_until = int(os.environ.get("DENSE_UNTIL", 300))
     for i in range(M):
         a, b = pairs[i]
         for key, st in res.items():
@@ -223,6 +227,8 @@ def main():
                     st["full"] += lv is None
                     last = counts[i + k - 1]
                     st["list"] = last if (i + k < M and counts[i + k] == last and pairs[i][0] != pairs[i][1]) else None
+                elif r.endswith("_d6"):
+                    k = batch_at(i, min(int(cap), 6) if i < dense_until else int(cap), r[:-3])
                 else:
                     k = batch_at(i, int(cap), r)
                 st["steps"] += 1
