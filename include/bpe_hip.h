@@ -70,7 +70,10 @@ int bpe_set_stream(bpe_ctx *ctx, void *hip_stream);
  *   "lb_tune", "scan_sup" (1024: the three-pass merge scans the tile summaries of streams of more tiles
  *   than this in three small launches instead of one workgroup);
  *   bpe_decode_batch_resident's copy pass: "dec_copy" (1 staged through an LDS window, 16-byte stores | 0 one token
- *   per lane, byte stores), "dec_window" (8192: bytes of that window), "dec_tile" (1024: tokens per workgroup tile). */
+ *   per lane, byte stores), "dec_window" (8192: bytes of that window), "dec_tile" (1024: tokens per workgroup tile);
+ *   bpe_rows_resident's pack kernel: "rows_tile" (4096: output elements per workgroup tile, 64..65536, a multiple of
+ *   4), "rows_stage" (1024: document starts a tile stages in LDS, 0..4096; a tile that holds more searches global
+ *   memory instead, and 0 makes every tile do so -- the cross-check form). */
 int bpe_set_option(bpe_ctx *ctx, const char *name, int64_t value);
 
 /* ---- input ----------------------------------------------------------------- */
@@ -262,6 +265,47 @@ int bpe_decode_batch_resident(bpe_ctx *ctx, const void *d_ids, int32_t id_width,
                               const uint64_t *d_doc_token_offsets, uint64_t k,
                               uint8_t *d_out, uint64_t out_cap, uint64_t *d_doc_byte_offsets,
                               uint64_t *n_bytes, uint64_t *bad_index);
+
+/* ---- resident training rows ---------------------------------------- */
+/* A flat id stream with document offsets -- what bpe_encode_batch_resident leaves in HBM -- to fixed-length rows, every
+ * large buffer ON THE DEVICE and owned by the caller:
+ *   d_ids            n token ids (int32), read in place, never written
+ *   d_doc_offsets    n_docs + 1 token positions (never NULL: one entry when n_docs = 0), validated on the device:
+ *                    ascending, none beyond n.  Document d is ids[off[d] : off[d + 1]); ids before off[0] or after
+ *                    off[n_docs] belong to no document and are never read into a row
+ *   the stream       seq_d = ids of document d, followed by sep_id with BPE_ROWS_HAS_SEP (an empty document is then a
+ *                    lone separator); stream = seq_0 | seq_1 | ..., T = its length
+ *   BPE_ROWS_PACK    row r, column j = stream[r * stride + j] while that position is < T, else pad_id; 1 <= stride <=
+ *                    row_len (stride = row_len: disjoint rows; row_len - 1: input and target overlap by one token).
+ *                    R = 0 if T = 0, else 1 + ceil(max(T - row_len, 0) / stride): only the last row can be partial.
+ *                    d_doc_index / d_pos (either may be NULL): int32 arrays of the rows' shape -- the document an
+ *                    element belongs to (a separator to the document it closes; pad: -1) and its index inside seq_d
+ *                    (pad: 0)
+ *   BPE_ROWS_PER_DOC R = n_docs; row d = seq_d cut to row_len -- the head, or the tail with BPE_ROWS_TRUNC_LEFT --
+ *                    then padded with pad_id on the right, or the left with BPE_ROWS_PAD_LEFT.  d_lengths (may be
+ *                    NULL): n_docs int32, min(len(seq_d), row_len).  stride is ignored
+ *   d_rows           rows_cap rows of row_len elements of row_width = 4 (int32) or 8 (int64) bytes, sep_id and pad_id
+ *                    sign-extended; NULL = only count
+ *   *n_rows          R (set whenever the offsets are valid, also on BPE_E_CAP)
+ *   *bad_doc         first entry of d_doc_offsets that descends or lies beyond n (~0 if none)
+ * BPE_E_ARG before any device work: row_len = 0, stride = 0 or > row_len in pack mode, row_width not 4 or 8, an unknown
+ * mode or flag (the per-document flags in pack mode included), d_doc_index / d_pos in per-document mode, d_lengths in
+ * pack mode.  BPE_E_LIMIT: n >= 2^32, or d_doc_index / d_pos with n + n_docs >= 2^31.  Bad offsets fail with BPE_E_ARG
+ * and *bad_doc; rows_cap < R fails with BPE_E_CAP; both write nothing.  Never writes outside the first R * row_len
+ * elements of d_rows (and of the companions), whatever their alignment.  Runs on the ctx's stream and synchronises it
+ * before returning; keeps no pointer of the caller's. */
+#define BPE_ROWS_PACK 0
+#define BPE_ROWS_PER_DOC 1
+#define BPE_ROWS_HAS_SEP 1u
+#define BPE_ROWS_TRUNC_LEFT 2u
+#define BPE_ROWS_PAD_LEFT 4u
+int bpe_rows_resident(bpe_ctx *ctx, const int32_t *d_ids, uint64_t n,
+                      const uint64_t *d_doc_offsets, uint64_t n_docs,
+                      int32_t mode, uint32_t flags, uint64_t row_len, uint64_t stride,
+                      int32_t sep_id, int32_t pad_id,
+                      void *d_rows, int32_t row_width, uint64_t rows_cap,
+                      int32_t *d_doc_index, int32_t *d_pos, int32_t *d_lengths,
+                      uint64_t *n_rows, uint64_t *bad_doc);
 
 /* ---- measurement ------------------------------------------------------------ */
 #define BPE_PROF_WIDEN 0

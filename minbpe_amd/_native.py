@@ -98,6 +98,8 @@ _SIGS = {
     "bpe_decode_set_sparse": (C.c_int, [_p, _p, _i32, _i32]),
     "bpe_decode_batch_resident": (C.c_int, [_p, _p, _i32, _u64, _p, _u64, _p, _u64, _p, C.POINTER(_u64),
                                             C.POINTER(_u64)]),
+    "bpe_rows_resident": (C.c_int, [_p, _p, _u64, _p, _u64, _i32, C.c_uint32, _u64, _u64, _i32, _i32, _p, _i32, _u64,
+                                    _p, _p, _p, C.POINTER(_u64), C.POINTER(_u64)]),
     "bpe_prof_reset": (C.c_int, [_p]),
     "bpe_prof_read": (C.c_int, [_p, _p, _p, _p]),
     "bpe_encode_uses_16bit": (C.c_int, [_p, C.c_int32]),
@@ -225,6 +227,26 @@ class OutputTooSmall(ValueError):
     def __init__(self, needed, msg):
         super().__init__(msg)
         self.needed = needed
+
+
+class BadDocOffsets(ValueError):
+    """bpe_rows_resident met document offsets that descend or lie beyond the ids; index = the first such entry."""
+
+    def __init__(self, index, msg):
+        super().__init__(msg)
+        self.index = index
+
+
+class RowsTooSmall(ValueError):
+    """bpe_rows_resident was given room for fewer rows than the batch makes; needed = that number."""
+
+    def __init__(self, needed, msg):
+        super().__init__(msg)
+        self.needed = needed
+
+
+ROWS_PACK, ROWS_PER_DOC = 0, 1
+ROWS_HAS_SEP, ROWS_TRUNC_LEFT, ROWS_PAD_LEFT = 1, 2, 4
 
 
 def _ptr(a):
@@ -559,6 +581,26 @@ class Engine:
             raise OutputTooSmall(int(nb.value), (_lib.bpe_last_error(self._h) or b"").decode())
         self._check(rc)
         return int(nb.value)
+
+    # -- resident training rows ------------------------------------------------------
+    def rows_resident(self, d_ids: int, n: int, d_doc_off: int, n_docs: int, mode: int, flags: int, row_len: int,
+                      stride: int, sep: int, pad: int, d_rows: int, row_width: int, rows_cap: int, d_doc_index: int = 0,
+                      d_pos: int = 0, d_lengths: int = 0) -> int:
+        """bpe_rows_resident: d_ids (n int32), d_doc_off (n_docs + 1 uint64), d_rows (rows_cap rows of row_len elements
+        of row_width = 4 or 8 bytes; 0 = only count) and the int32 companions (0 = none) are device addresses (e.g.
+        torch tensor.data_ptr()).  mode ROWS_PACK / ROWS_PER_DOC, flags ROWS_HAS_SEP | ROWS_TRUNC_LEFT | ROWS_PAD_LEFT.
+        Returns the number of rows.  Offsets that descend or pass n raise BadDocOffsets(entry); too little room raises
+        RowsTooSmall."""
+        nr, bad = _u64(0), _u64(0)
+        rc = _lib.bpe_rows_resident(self._h, C.c_void_p(d_ids), n, C.c_void_p(d_doc_off), n_docs, mode, flags, row_len,
+                                    stride, sep, pad, C.c_void_p(d_rows), row_width, rows_cap, C.c_void_p(d_doc_index),
+                                    C.c_void_p(d_pos), C.c_void_p(d_lengths), C.byref(nr), C.byref(bad))
+        if rc == BPE_E_ARG and bad.value != 0xFFFFFFFFFFFFFFFF:
+            raise BadDocOffsets(int(bad.value), (_lib.bpe_last_error(self._h) or b"").decode())
+        if rc == BPE_E_CAP:
+            raise RowsTooSmall(int(nr.value), (_lib.bpe_last_error(self._h) or b"").decode())
+        self._check(rc)
+        return int(nr.value)
 
     # -- measurement ----------------------------------------------------------------
     def prof_reset(self):

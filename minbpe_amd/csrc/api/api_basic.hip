@@ -161,6 +161,13 @@ int bpe_set_option(bpe_ctx *c, const char *name, int64_t value) {
     } else if (!strcmp(name, "dec_tile")) {
         if (value < 256 || value > 16384 || value % 256) return fail(c, BPE_E_ARG, "dec_tile: 256..16384 tokens, a multiple of 256");
         c->dec_tile = (int)value;
+    } else if (!strcmp(name, "rows_tile")) {
+        if (value < 64 || value > ROWS_TILE_MAX || value % ROWS_V)
+            return fail(c, BPE_E_ARG, "rows_tile: 64..%u elements, a multiple of %u", ROWS_TILE_MAX, ROWS_V);
+        c->rows_tile = (int)value;
+    } else if (!strcmp(name, "rows_stage")) {
+        if (value < 0 || value > ROWS_STAGE_MAX) return fail(c, BPE_E_ARG, "rows_stage: 0..%u document starts", ROWS_STAGE_MAX);
+        c->rows_stage = (int)value;
     } else if (!strcmp(name, "prof_stride")) {
         if (value < 1 || value > 1024) return fail(c, BPE_E_ARG, "prof_stride must be 1..1024");
         c->prof_stride = (int)value;

@@ -229,6 +229,9 @@ struct bpe_ctx {
     int dec_copy = 1;        // option "dec_copy": 1 = k_decode_copy_staged (LDS window, 16-byte stores) | 0 = k_decode_copy (one token per lane)
     int dec_window = 8192;   // option "dec_window": bytes of the staged copy's LDS window
     int dec_tile = 1024;     // option "dec_tile": tokens per workgroup tile of the staged copy
+    // bpe_rows_resident (k_rows.hip)
+    int rows_tile = 4096;    // option "rows_tile": output elements per workgroup tile
+    int rows_stage = 1024;   // option "rows_stage": document starts a tile stages in LDS (0: every lane searches global memory, the cross-check form)
 
     int mode = 1;     // 0 recount | 1 delta
     int profile = 0;  // 0 off | 1 hipEvents around the merge pass | 2 around every kernel class

@@ -62,4 +62,5 @@
 #undef BPE_G
 #include "kernels/k_encode.hip"
 #include "kernels/k_decode.hip"
+#include "kernels/k_rows.hip"
 #include "kernels/k_util.hip"

@@ -28,10 +28,14 @@ _NATIVE_SPLIT = {GPT2_SPLIT_PATTERN: 2, GPT4_SPLIT_PATTERN: 4}
 _engines = {}
 
 
+def _default_device() -> int:
+    return int(os.environ.get("MINBPE_AMD_DEVICE", os.environ.get("LOCAL_RANK", "0")))
+
+
 def engine(device=None) -> "_native.Engine":
     """Process-wide engine (one ctx) per GPU, created on first use."""
     if device is None:
-        device = int(os.environ.get("MINBPE_AMD_DEVICE", os.environ.get("LOCAL_RANK", "0")))
+        device = _default_device()
     if device not in _engines:
         _engines[device] = _native.Engine(device)
     return _engines[device]
@@ -73,6 +77,18 @@ def replace_control_characters(s: str) -> str:
 
 def render_token(t: bytes) -> str:
     return replace_control_characters(t.decode("utf-8", errors="replace"))
+
+
+def rows_count(total, row_len, stride):
+    """Rows of `row_len` elements taken every `stride` positions (1 <= stride <= row_len) from a stream of `total`
+    elements, as rows_resident(mode="pack") lays them out: 0 for an empty stream, else 1 + ceil(max(total - row_len, 0)
+    / stride) -- only the last row can be partial."""
+    total, row_len, stride = int(total), int(row_len), int(stride)
+    if row_len < 1 or not 1 <= stride <= row_len or total < 0:
+        raise ValueError("rows_count needs total >= 0 and 1 <= stride <= row_len")
+    if total == 0:
+        return 0
+    return 1 + (max(total - row_len, 0) + stride - 1) // stride
 
 
 def _concat_chunks(chunks):
@@ -297,6 +313,131 @@ class Tokenizer:
         res = out[:total]
         return res if doc_offsets is None else (res, boff)
 
+    # -- fixed-length rows from ids that live in HBM ---------------------
+    def rows_resident(self, ids, doc_offsets, row_len, *, stride=None, sep=None, pad=0, mode="pack", truncate="right",
+                      pad_side="right", dtype=None, drop_last=False, return_doc_index=False, return_positions=False,
+                      out=None, _total=None):
+        """Fixed-length rows for a model from token ids that live in HBM, made on the device; not in the reference.
+        `ids` is a 1-D contiguous int32 torch tensor on the GPU (what encode_ordinary_batch_resident returns),
+        `doc_offsets` n_docs + 1 token positions -- an integer tensor on the same GPU or anything np.asarray takes --,
+        document d being ids[doc_offsets[d]:doc_offsets[d + 1]].  sep: an id (or the text of a registered special token)
+        appended to every document; pad: the id that fills what is left.  dtype: torch.int64 (default) or torch.int32.
+
+        mode="pack": the documents joined into one stream and cut into rows of row_len every `stride` positions
+        (default row_len: disjoint rows; row_len - 1: input and target overlap by one token).  Returns the [R, row_len]
+        tensor, R = rows_count(len(stream), row_len, stride); with return_doc_index / return_positions also int32
+        tensors of the same shape: the document of every element (pad: -1) and its index inside its document (pad: 0).
+        drop_last drops the last row if it is partial.
+
+        mode="per_doc": one row per document, cut to row_len (truncate="right" keeps the head, "left" the tail) and padded
+        on pad_side.  Returns (rows [n_docs, row_len], lengths int32 [n_docs]).
+
+        out: a contiguous tensor of `dtype` on the same GPU to write the rows into (the view of the rows written is
+        returned; ValueError if it is too small).  Nothing but counters crosses PCIe."""
+        import torch
+        # -- values: checked before any tensor is looked at, and all of it before the engine exists
+        if isinstance(row_len, bool) or not isinstance(row_len, (int, np.integer)) or row_len < 1:
+            raise ValueError("row_len must be a positive integer")
+        row_len = int(row_len)
+        if mode not in ("pack", "per_doc"):
+            raise ValueError(f"mode={mode!r} not understood: 'pack' or 'per_doc'")
+        pack = mode == "pack"
+        if truncate not in ("right", "left") or pad_side not in ("right", "left"):
+            raise ValueError("truncate and pad_side are 'right' or 'left'")
+        if pack:
+            if truncate != "right" or pad_side != "right":
+                raise ValueError("truncate / pad_side belong to mode='per_doc'")
+            stride = row_len if stride is None else stride
+            if isinstance(stride, bool) or not isinstance(stride, (int, np.integer)) or not 1 <= stride <= row_len:
+                raise ValueError("stride must be an integer in 1..row_len")
+            stride = int(stride)
+        else:
+            if stride is not None or drop_last or return_doc_index or return_positions:
+                raise ValueError("stride, drop_last, return_doc_index and return_positions belong to mode='pack'")
+            stride = row_len
+        if isinstance(sep, str):
+            sep = self.special_tokens[sep]  # (KeyError: not a registered special token)
+        for name, v in (("sep", sep), ("pad", pad)):
+            if v is None and name == "sep":
+                continue
+            if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or not -2**31 <= v < 2**31:
+                raise ValueError(f"{name} must be an integer that fits int32")
+        dtype = torch.int64 if dtype is None else dtype
+        if dtype not in (torch.int32, torch.int64):
+            raise ValueError("dtype must be torch.int32 or torch.int64")
+        # -- tensors
+        if not isinstance(ids, torch.Tensor) or ids.dim() != 1 or ids.dtype != torch.int32 or not ids.is_contiguous():
+            raise TypeError("ids must be a 1-D contiguous int32 torch tensor on the GPU")
+        dev = ids.device
+        if isinstance(doc_offsets, torch.Tensor):
+            if doc_offsets.device != dev or doc_offsets.dtype not in (torch.int32, torch.int64):
+                raise TypeError("doc_offsets must be an integer tensor on the device of ids")
+            n_off = doc_offsets.numel()
+        else:
+            doc_offsets = np.asarray(doc_offsets)
+            if doc_offsets.size and doc_offsets.dtype.kind not in "iu":
+                raise TypeError("doc_offsets must be integers")
+            n_off = doc_offsets.size
+        if n_off < 1:
+            raise ValueError("doc_offsets needs n_docs + 1 entries")
+        if out is not None:
+            if not isinstance(out, torch.Tensor) or out.device != dev or out.dtype != dtype or not out.is_contiguous():
+                raise TypeError("out must be a contiguous tensor of `dtype` on the device of ids")
+        if not ids.is_cuda:
+            raise TypeError("ids must be a 1-D contiguous int32 torch tensor on the GPU")
+        # -- the device
+        n, n_docs = ids.numel(), n_off - 1
+        if isinstance(doc_offsets, torch.Tensor):
+            doff = doc_offsets.to(torch.int64).contiguous().reshape(-1)
+        else:
+            doff = torch.from_numpy(np.ascontiguousarray(doc_offsets, dtype=np.int64).reshape(-1)).to(dev)
+        flags = (_native.ROWS_HAS_SEP if sep is not None else 0) | (_native.ROWS_TRUNC_LEFT if truncate == "left" else 0) \
+            | (_native.ROWS_PAD_LEFT if pad_side == "left" else 0)
+        width = 4 if dtype == torch.int32 else 8
+        eng = engine(dev.index)
+        torch.cuda.current_stream(dev).synchronize()  # the caller's pending writes to ids (and the upload above) are done
+
+        def call(dst, cap, comps=(None, None, None)):
+            try:
+                return eng.rows_resident(ids.data_ptr(), n, doff.data_ptr(), n_docs,
+                                         _native.ROWS_PACK if pack else _native.ROWS_PER_DOC, flags, row_len, stride,
+                                         0 if sep is None else int(sep), int(pad), 0 if dst is None else dst.data_ptr(),
+                                         width, cap, *(0 if t is None else t.data_ptr() for t in comps))
+            except _native.RowsTooSmall as e:
+                raise ValueError(f"out holds {cap} rows of {row_len}, the batch makes {e.needed}") from None
+
+        if not pack:
+            R = n_docs
+        elif _total is not None:  # (the caller knows the stream's length: no counting call)
+            R = rows_count(_total, row_len, stride)
+        else:
+            R = call(None, 0)
+        cap = R if out is None else out.numel() // row_len
+        if out is None:
+            out = torch.empty((R, row_len), dtype=dtype, device=dev)
+        elif cap == 0 and R:  # (no room at all is a count-only call to the library)
+            raise ValueError(f"out holds 0 rows of {row_len}, the batch makes {R}")
+        comps = [None, None, None]
+        if return_doc_index:
+            comps[0] = torch.empty((R, row_len), dtype=torch.int32, device=dev)
+        if return_positions:
+            comps[1] = torch.empty((R, row_len), dtype=torch.int32, device=dev)
+        if not pack:
+            comps[2] = torch.empty(n_docs, dtype=torch.int32, device=dev)
+        torch.cuda.current_stream(dev).synchronize()
+        R = call(out, cap, comps)
+        rows = out.reshape(-1)[:R * row_len].view(R, row_len)
+        if not pack:
+            return rows, comps[2]
+        keep = R
+        if drop_last and R:
+            total = _total if _total is not None else \
+                int((doff[-1] - doff[0]).item()) + (n_docs if sep is not None else 0)
+            if (R - 1) * stride + row_len > total:
+                keep = R - 1
+        res = [rows[:keep]] + [t[:keep] for t in comps[:2] if t is not None]
+        return res[0] if len(res) == 1 else tuple(res)
+
     # -- persistence (file formats of base.py:97-165, byte for byte) -----------------
     def save(self, file_prefix):
         lines = ["minbpe v1", f"{self.pattern}", f"{len(self.special_tokens)}"]
@@ -460,6 +601,53 @@ class RegexTokenizer(Tokenizer):
             first = np.array(first, dtype=np.uint64)
         ids, out_off = self._encode_flat(data, offs)
         return ids, out_off[first.astype(np.int64)]
+
+    def encode_ordinary_batch_resident(self, texts, device=None):
+        """encode_ordinary_batch() with the ids left in HBM: returns (ids, doc_offsets), an int32 torch tensor on the
+        GPU holding the ids of all texts back to back (a view of the buffer the engine wrote) and len(texts) + 1 int64
+        offsets on the same GPU.  The host splits the texts and uploads their bytes once; ids and offsets never come
+        back.  device: the GPU's index (default: the process-wide engine's)."""
+        import torch
+        if device is None:
+            device = _default_device()
+        dev = torch.device("cuda", device) if isinstance(device, int) else torch.device(device)
+        if dev.type != "cuda" or dev.index is None:
+            raise ValueError("device must name one GPU: an index, or 'cuda:<index>'")
+        enc = [t.encode("utf-8") for t in texts]
+        if not any(enc):  # nothing to encode: no engine call
+            return torch.empty(0, dtype=torch.int32, device=dev), torch.zeros(len(enc) + 1, dtype=torch.int64, device=dev)
+        which = _NATIVE_SPLIT.get(self.compiled_pattern.pattern)
+        if which is not None:
+            data = b"".join(enc)
+            doff = np.zeros(len(enc), dtype=np.uint64)
+            np.cumsum(np.fromiter((len(e) for e in enc[:-1]), dtype=np.uint64, count=len(enc) - 1), out=doff[1:])
+            offs, first = _native.split_docs(data, doff, which)
+        else:  # any other pattern: the regex module, one text at a time
+            pieces, first = [], [0]
+            for t in texts:
+                pieces += [p for p in self._split(t) if p]
+                first.append(len(pieces))
+            data, offs = _concat_chunks(pieces)
+        first = np.ascontiguousarray(first, dtype=np.int64)[:len(enc) + 1]
+        pairs, mids = self._merge_table()
+        data = self._prepare_chunk(data)
+        d_bytes = torch.from_numpy(np.frombuffer(bytearray(data), dtype=np.uint8)).to(dev)
+        d_offs = torch.from_numpy(np.ascontiguousarray(offs, dtype=np.uint64).view(np.int64)).to(dev)
+        d_first = torch.from_numpy(first).to(dev)
+        d_ids = torch.empty(len(data), dtype=torch.int32, device=dev)
+        d_ooff = torch.empty(len(offs) + 1, dtype=torch.int64, device=dev)
+        torch.cuda.current_stream(dev).synchronize()  # the uploads are done
+        total = engine(dev.index).encode_batch_resident(pairs, mids, d_bytes.data_ptr(), len(data), d_offs.data_ptr(),
+                                                        len(offs), d_ids.data_ptr(), d_ooff.data_ptr())
+        return d_ids[:total], d_ooff[d_first]
+
+    def encode_batch_rows(self, texts, row_len, device=None, **kw):
+        """encode_ordinary_batch_resident() and rows_resident() in one call: texts to fixed-length rows on the GPU
+        (keywords as rows_resident's).  The stream's length is known here, so the rows are sized by rows_count()."""
+        ids, doff = self.encode_ordinary_batch_resident(texts, device)
+        if kw.get("mode", "pack") == "pack" and "_total" not in kw:
+            kw["_total"] = ids.numel() + (len(doff) - 1 if kw.get("sep") is not None else 0)
+        return self.rows_resident(ids, doff, row_len, **kw)
 
     def encode(self, text, allowed_special="none_raise"):
         if allowed_special == "all":
