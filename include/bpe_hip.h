@@ -73,7 +73,8 @@ int bpe_set_stream(bpe_ctx *ctx, void *hip_stream);
  *   per lane, byte stores), "dec_window" (8192: bytes of that window), "dec_tile" (1024: tokens per workgroup tile);
  *   bpe_rows_resident's pack kernel: "rows_tile" (4096: output elements per workgroup tile, 64..65536, a multiple of
  *   4), "rows_stage" (1024: document starts a tile stages in LDS, 0..4096; a tile that holds more searches global
- *   memory instead, and 0 makes every tile do so -- the cross-check form). */
+ *   memory instead, and 0 makes every tile do so -- the cross-check form);
+ *   bpe_token_spans_resident's emit kernel: "spans_stage" (1024, 0..4096: the same for its tiles of 1024 tokens). */
 int bpe_set_option(bpe_ctx *ctx, const char *name, int64_t value);
 
 /* ---- input ----------------------------------------------------------------- */
@@ -306,6 +307,46 @@ int bpe_rows_resident(bpe_ctx *ctx, const int32_t *d_ids, uint64_t n,
                       void *d_rows, int32_t row_width, uint64_t rows_cap,
                       int32_t *d_doc_index, int32_t *d_pos, int32_t *d_lengths,
                       uint64_t *n_rows, uint64_t *bad_doc);
+
+/* ---- resident token spans ------------------------------------------- */
+/* The offset mapping of a batch of token ids that live in HBM: for every token, where it lies in the text its document
+ * decodes to, in bytes and in characters.  Every large buffer is ON THE DEVICE and owned by the caller.
+ *   e(t)             the bytes of table entry t: the vocab as uploaded (bpe_decode_set_vocab / bpe_decode_set_sparse),
+ *                    ids resolved as bpe_decode_batch_resident resolves them
+ *   lead             a byte b with (b & 0xC0) != 0x80: ASCII, UTF-8 start bytes and bytes that are no UTF-8 at all;
+ *                    only 10xxxxxx is not
+ *   len_i, leads_i   len(e(t_i)) and the number of lead bytes in e(t_i), for token i of the batch
+ *   cont_i           1 if len_i > 0 and the first byte of e(t_i) is not a lead, else 0
+ *   B_i, C_i         the sums of len_j and of leads_j over the tokens j < i of the same document
+ *   byte span        (B_i, B_i + len_i)
+ *   char span        (max(C_i - cont_i, 0), C_i + leads_i)
+ * Documents: d_doc_offsets = NULL (n_docs = 0): the whole batch is one document.  Otherwise n_docs + 1 token positions,
+ * validated on the device as in bpe_rows_resident (ascending, none beyond n; empty documents are fine), document d being
+ * tokens [off[d], off[d + 1]); a token before off[0] or at or after off[n_docs] belongs to no document, its spans are
+ * (-1, -1).
+ * If the bytes a document decodes to are valid UTF-8 of a string s, then s.encode()[b0:b1] == e(t_i), and for a
+ * non-empty token s[c0:c1] is the shortest run of code points whose encoding covers those bytes (two byte tokens that
+ * split one two-byte character both get (k, k + 1)); an empty token gets c0 == c1.  On invalid UTF-8 the numbers are
+ * still the ones defined above; the clamp at 0 only matters there.
+ *   d_ids, id_width  n ids of 4 (int32) or 8 (int64) bytes, read in place, never written
+ *   d_byte_spans, d_char_spans   int64 [n][2] each, 8-byte aligned (16-byte stores are used where the address allows);
+ *                    either may be NULL, both NULL = validate and count only.  Nothing outside the first 2 n elements of
+ *                    either array is written
+ *   *n_bytes, *n_chars   the batch's totals: sum of len_i, sum of leads_i (documents or not)
+ *   *bad_index       first position whose id does not decode (~0 if none)
+ *   *bad_doc         first entry of d_doc_offsets that descends or lies beyond n (~0 if none)
+ * BPE_E_STATE without a vocab table.  BPE_E_ARG: id_width not 4 or 8, d_doc_offsets = NULL with n_docs > 0, a span array
+ * that is not 8-byte aligned, an id that does not decode (*bad_index), bad offsets (*bad_doc); on either of the last
+ * two nothing is written to the span arrays.  BPE_E_LIMIT: a table entry of 2^31 lead bytes or more, n >= 2^43,
+ * n_docs >= 2^32.  n = 0 is BPE_OK with totals 0.  The UTF-8 meta of the table (leads and cont of every entry) is made on
+ * the device by the first call after a bpe_decode_set_vocab.  Runs on the ctx's stream and synchronises it before
+ * returning; keeps no pointer of the caller's; only counters cross PCIe.  The ctx's decode scratch is shared with
+ * bpe_decode_batch: a result of that call not yet read is dropped. */
+int bpe_token_spans_resident(bpe_ctx *ctx, const void *d_ids, int32_t id_width, uint64_t n,
+                             const uint64_t *d_doc_offsets, uint64_t n_docs,
+                             int64_t *d_byte_spans, int64_t *d_char_spans,
+                             uint64_t *n_bytes, uint64_t *n_chars,
+                             uint64_t *bad_index, uint64_t *bad_doc);
 
 /* ---- measurement ------------------------------------------------------------ */
 #define BPE_PROF_WIDEN 0

@@ -100,6 +100,8 @@ _SIGS = {
                                             C.POINTER(_u64)]),
     "bpe_rows_resident": (C.c_int, [_p, _p, _u64, _p, _u64, _i32, C.c_uint32, _u64, _u64, _i32, _i32, _p, _i32, _u64,
                                     _p, _p, _p, C.POINTER(_u64), C.POINTER(_u64)]),
+    "bpe_token_spans_resident": (C.c_int, [_p, _p, _i32, _u64, _p, _u64, _p, _p, C.POINTER(_u64), C.POINTER(_u64),
+                                           C.POINTER(_u64), C.POINTER(_u64)]),
     "bpe_prof_reset": (C.c_int, [_p]),
     "bpe_prof_read": (C.c_int, [_p, _p, _p, _p]),
     "bpe_encode_uses_16bit": (C.c_int, [_p, C.c_int32]),
@@ -601,6 +603,24 @@ class Engine:
             raise RowsTooSmall(int(nr.value), (_lib.bpe_last_error(self._h) or b"").decode())
         self._check(rc)
         return int(nr.value)
+
+    # -- resident token spans --------------------------------------------------------
+    def token_spans_resident(self, d_ids: int, id_width: int, n: int, d_doc_off: int = 0, n_docs: int = 0,
+                             d_byte_spans: int = 0, d_char_spans: int = 0):
+        """bpe_token_spans_resident: d_ids (n ids of id_width = 4 or 8 bytes), d_doc_off (n_docs + 1 uint64; 0 = the batch
+        is one document) and the two int64 [n, 2] span arrays (0 = not wanted) are device addresses (e.g. torch
+        tensor.data_ptr()).  Returns (total bytes, total characters) of the batch.  An id that does not decode raises
+        InvalidToken(position); offsets that descend or pass n raise BadDocOffsets(entry)."""
+        nb, nc, bad, bad_doc = _u64(0), _u64(0), _u64(0), _u64(0)
+        rc = _lib.bpe_token_spans_resident(self._h, C.c_void_p(d_ids), id_width, n, C.c_void_p(d_doc_off), n_docs,
+                                           C.c_void_p(d_byte_spans), C.c_void_p(d_char_spans), C.byref(nb), C.byref(nc),
+                                           C.byref(bad), C.byref(bad_doc))
+        if rc == BPE_E_ARG and bad.value != 0xFFFFFFFFFFFFFFFF:
+            raise InvalidToken(int(bad.value))
+        if rc == BPE_E_ARG and bad_doc.value != 0xFFFFFFFFFFFFFFFF:
+            raise BadDocOffsets(int(bad_doc.value), (_lib.bpe_last_error(self._h) or b"").decode())
+        self._check(rc)
+        return int(nb.value), int(nc.value)
 
     # -- measurement ----------------------------------------------------------------
     def prof_reset(self):

@@ -68,7 +68,7 @@ void bpe_destroy(bpe_ctx *c) {
                     c->d_dp_folded, c->d_dp_table, c->d_dp_key, c->d_meta[0], c->d_meta[1], c->d_slot_lens,
                     c->d_slot_off, c->d_slot_bsum, c->d_ids2, c->d_hdr[0], c->d_hdr[1],
                     c->d_dec_blob, c->d_dec_out, c->d_dec_voff, c->d_dec_off, c->d_dec_bsum, c->d_dec_ids,
-                    c->d_dec_len, c->d_dec_sparse, c->d_wexp, c->d_round_lb, c->d_dp_ckey, c->d_dp_cfold, c->d_hdr2[0], c->d_hdr2[1], c->d_stage, c->d_idx, c->d_idx_tmp, c->d_idx_dirty, c->d_removed, c->d_smask, c->d_cand, c->d_dbits, c->d_lean_res, c->d_lean_sum, c->d_enc_tab, c->d_enc_rep, c->d_enc_mid, c->d_enc_midn, c->d_chain_req, c->d_pool, c->d_pool_gather, c->d_enc_huge};
+                    c->d_dec_len, c->d_dec_sparse, c->d_dec_meta, c->d_spn_off, c->d_spn_bsum, c->d_spn_base, c->d_wexp, c->d_round_lb, c->d_dp_ckey, c->d_dp_cfold, c->d_hdr2[0], c->d_hdr2[1], c->d_stage, c->d_idx, c->d_idx_tmp, c->d_idx_dirty, c->d_removed, c->d_smask, c->d_cand, c->d_dbits, c->d_lean_res, c->d_lean_sum, c->d_enc_tab, c->d_enc_rep, c->d_enc_mid, c->d_enc_midn, c->d_chain_req, c->d_pool, c->d_pool_gather, c->d_enc_huge};
     for (void *p : ptrs)
         if (p) (void)hipFree(p);
     if (c->h_rec) (void)hipHostFree(c->h_rec);
@@ -168,6 +168,9 @@ int bpe_set_option(bpe_ctx *c, const char *name, int64_t value) {
     } else if (!strcmp(name, "rows_stage")) {
         if (value < 0 || value > ROWS_STAGE_MAX) return fail(c, BPE_E_ARG, "rows_stage: 0..%u document starts", ROWS_STAGE_MAX);
         c->rows_stage = (int)value;
+    } else if (!strcmp(name, "spans_stage")) {
+        if (value < 0 || value > SPANS_STAGE_MAX) return fail(c, BPE_E_ARG, "spans_stage: 0..%u document starts", SPANS_STAGE_MAX);
+        c->spans_stage = (int)value;
     } else if (!strcmp(name, "prof_stride")) {
         if (value < 1 || value > 1024) return fail(c, BPE_E_ARG, "prof_stride must be 1..1024");
         c->prof_stride = (int)value;

@@ -232,6 +232,13 @@ struct bpe_ctx {
     // bpe_rows_resident (k_rows.hip)
     int rows_tile = 4096;    // option "rows_tile": output elements per workgroup tile
     int rows_stage = 1024;   // option "rows_stage": document starts a tile stages in LDS (0: every lane searches global memory, the cross-check form)
+    // bpe_token_spans_resident (k_spans.hip): leads | cont << 31 of every table entry, made on the device by the first
+    // call after a bpe_decode_set_vocab; the second scan channel and the documents' bases (grow-only)
+    uint32_t *d_dec_meta = nullptr;
+    unsigned long long *d_spn_off = nullptr, *d_spn_bsum = nullptr, *d_spn_base = nullptr;
+    uint64_t cap_dec_meta = 0, cap_spn_n = 0, cap_spn_docs = 0;
+    bool dec_meta_valid = false;
+    int spans_stage = 1024;  // option "spans_stage": document starts a tile stages in LDS (0: every lane searches global memory, the cross-check form)
 
     int mode = 1;     // 0 recount | 1 delta
     int profile = 0;  // 0 off | 1 hipEvents around the merge pass | 2 around every kernel class

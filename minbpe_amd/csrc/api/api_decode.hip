@@ -16,6 +16,7 @@ extern "C" int bpe_decode_set_vocab(bpe_ctx *c, const uint8_t *vocab_bytes, cons
     HIPCHK(c, hipSetDevice(c->device));
     c->dec_have_vocab = false;
     c->dec_have_result = false;
+    c->dec_meta_valid = false;  // (bpe_token_spans_resident makes the entries' UTF-8 meta anew, on the device)
     if (nb + 16 > c->cap_dec_blob) {
         TRY(dev_realloc(c, c->d_dec_blob, (size_t)nb + 16));
         c->cap_dec_blob = nb + 16;

@@ -63,4 +63,5 @@
 #include "kernels/k_encode.hip"
 #include "kernels/k_decode.hip"
 #include "kernels/k_rows.hip"
+#include "kernels/k_spans.hip"
 #include "kernels/k_util.hip"

@@ -58,6 +58,23 @@ k_decode_doc_offsets(const unsigned long long *__restrict__ off, uint64_t n, uns
 // ---------------------------------------------------------------------------
 // resident batch decode (bpe_decode_batch_resident): ids of the caller's, 4 or 8 bytes wide, in HBM
 
+// the table index of id v, 0xFFFFFFFF if it does not decode (shared with the length pass of k_spans.hip)
+__device__ __forceinline__ uint32_t decode_resolve(long long v, uint32_t V_dense, const int32_t *__restrict__ sparse,
+                                                   uint32_t n_sparse) {
+    uint32_t t = 0xFFFFFFFFu;
+    if (v >= 0 && v < (long long)V_dense) {
+        t = (uint32_t)v;
+    } else if (v >= -2147483648ll && v <= 2147483647ll) {
+        uint32_t lo = 0, hi = n_sparse;  // first entry >= v
+        while (lo < hi) {
+            const uint32_t mid = (lo + hi) >> 1;
+            if ((long long)sparse[mid] < v) lo = mid + 1; else hi = mid;
+        }
+        if (lo < n_sparse && (long long)sparse[lo] == v) t = V_dense + lo;
+    }
+    return t;
+}
+
 // Length pass.  An id in [0, V_dense) is its own table index; any other id is looked up in the sorted sparse list
 // (special tokens: a few to a few hundred entries, cache resident), entry j being table index V_dense + j.  A 64-bit id is
 // compared at its full width: one outside the int32 range matches nothing.  Writes the RESOLVED table index next to the
@@ -69,18 +86,7 @@ k_decode_res_len(const IdT *__restrict__ ids, uint64_t n, const unsigned long lo
                  uint32_t *__restrict__ len, unsigned long long *bad) {
     const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
     for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
-        const long long v = (long long)ids[i];
-        uint32_t t = 0xFFFFFFFFu;
-        if (v >= 0 && v < (long long)V_dense) {
-            t = (uint32_t)v;
-        } else if (v >= -2147483648ll && v <= 2147483647ll) {
-            uint32_t lo = 0, hi = n_sparse;  // first entry >= v
-            while (lo < hi) {
-                const uint32_t mid = (lo + hi) >> 1;
-                if ((long long)sparse[mid] < v) lo = mid + 1; else hi = mid;
-            }
-            if (lo < n_sparse && (long long)sparse[lo] == v) t = V_dense + lo;
-        }
+        const uint32_t t = decode_resolve((long long)ids[i], V_dense, sparse, n_sparse);
         uint32_t L = 0;
         if (t != 0xFFFFFFFFu)
             L = (uint32_t)(voff[t + 1] - voff[t]);

@@ -313,6 +313,100 @@ class Tokenizer:
         res = out[:total]
         return res if doc_offsets is None else (res, boff)
 
+    # -- the offset mapping of ids that live in HBM -----------------------
+    _SPAN_UNITS = ("char", "byte", "both")
+
+    def token_spans_resident(self, ids, doc_offsets=None, *, unit="char"):
+        """Where every token lies in the text its document decodes to, computed on the device; not in the reference
+        (whose users loop over `vocab[idx]`).  `ids` is what decode_batch_resident takes: a 1-D contiguous int32 or int64
+        torch tensor on the GPU.  doc_offsets: n_docs + 1 token positions -- an integer tensor on the same GPU or anything
+        np.asarray takes --, document d being ids[doc_offsets[d]:doc_offsets[d + 1]] and every span counted from its
+        document's start; tokens outside every document get (-1, -1).  Without it the batch is one document.
+
+        unit="char": an int64 [n, 2] tensor on the GPU of (start, end) in characters -- for ids that encode_ordinary made
+        of a text, text[start:end] is the shortest run of characters that covers the token's bytes (the byte tokens
+        that split one character all get that character; an empty token gets start == end).  unit="byte": the same in
+        bytes of text.encode("utf-8").  unit="both": the pair (byte_spans, char_spans).  Unknown ids raise what decode()
+        raises, for the first such id; offsets that descend or pass len(ids) raise ValueError.  Nothing but counters
+        crosses PCIe."""
+        import torch
+        if unit not in self._SPAN_UNITS:
+            raise ValueError(f"unit={unit!r} not understood: 'char', 'byte' or 'both'")
+        if not isinstance(ids, torch.Tensor) or ids.dim() != 1 or not ids.is_contiguous() \
+                or ids.dtype not in (torch.int32, torch.int64):
+            raise TypeError("ids must be a 1-D contiguous int32 or int64 torch tensor on the GPU")
+        dev = ids.device
+        if doc_offsets is not None:
+            if isinstance(doc_offsets, torch.Tensor):
+                if doc_offsets.device != dev or doc_offsets.dtype not in (torch.int32, torch.int64):
+                    raise TypeError("doc_offsets must be an integer tensor on the device of ids")
+            else:
+                doc_offsets = np.asarray(doc_offsets)
+                if doc_offsets.size and doc_offsets.dtype.kind not in "iu":
+                    raise TypeError("doc_offsets must be integers")
+            if (doc_offsets.numel() if isinstance(doc_offsets, torch.Tensor) else doc_offsets.size) < 1:
+                raise ValueError("doc_offsets needs n_docs + 1 entries")
+        if not ids.is_cuda:
+            raise TypeError("ids must be a 1-D contiguous int32 or int64 torch tensor on the GPU")
+        blob, offs, V, sparse_ids = self._decode_table_resident()
+        eng = engine(dev.index)
+        owner = getattr(eng, "_decode_owner", (None, False))
+        if owner[0] is not blob or not owner[1]:
+            eng.decode_set_vocab(blob, offs)
+            eng.decode_set_sparse(sparse_ids, V)
+            eng._decode_owner = (blob, True)
+        n, width = ids.numel(), ids.element_size()
+        doff = None
+        if doc_offsets is not None:
+            if isinstance(doc_offsets, torch.Tensor):
+                doff = doc_offsets.to(torch.int64).contiguous().reshape(-1)
+            else:
+                doff = torch.from_numpy(np.ascontiguousarray(doc_offsets, dtype=np.int64).reshape(-1)).to(dev)
+        bspans = torch.empty((n, 2), dtype=torch.int64, device=dev) if unit != "char" else None
+        cspans = torch.empty((n, 2), dtype=torch.int64, device=dev) if unit != "byte" else None
+        torch.cuda.current_stream(dev).synchronize()  # the caller's pending writes to ids (and the upload above) are done
+        try:
+            eng.token_spans_resident(ids.data_ptr(), width, n, 0 if doff is None else doff.data_ptr(),
+                                     0 if doff is None else doff.numel() - 1,
+                                     0 if bspans is None else bspans.data_ptr(), 0 if cspans is None else cspans.data_ptr())
+        except _native.InvalidToken as e:
+            raise self._invalid_token(int(ids[e.args[0]].item())) from None
+        return cspans if unit == "char" else bspans if unit == "byte" else (bspans, cspans)
+
+    def token_spans(self, ids, doc_offsets=None, *, unit="char", device=None):
+        """token_spans_resident() for ids on the host (a list or an array of integers): NumPy int64 [n, 2] (a pair of
+        them for unit="both").  device: the GPU's index (default: the process-wide engine's)."""
+        if unit not in self._SPAN_UNITS:
+            raise ValueError(f"unit={unit!r} not understood: 'char', 'byte' or 'both'")
+        arr = np.asarray(ids)
+        if arr.size and arr.dtype.kind not in "iu":
+            raise TypeError("token ids must be integers")
+        if arr.ndim > 1:
+            raise TypeError("token ids must be a flat list or a 1-D array")
+        arr = np.ascontiguousarray(arr.astype(np.int64, copy=False).reshape(-1))
+        if doc_offsets is not None:
+            doc_offsets = np.asarray(doc_offsets)
+            if doc_offsets.size and doc_offsets.dtype.kind not in "iu":
+                raise TypeError("doc_offsets must be integers")
+        import torch
+        if device is None:
+            device = _default_device()
+        dev = torch.device("cuda", device) if isinstance(device, int) else torch.device(device)
+        if dev.type != "cuda" or dev.index is None:
+            raise ValueError("device must name one GPU: an index, or 'cuda:<index>'")
+        res = self.token_spans_resident(torch.from_numpy(arr).to(dev), doc_offsets, unit=unit)
+        return tuple(t.cpu().numpy() for t in res) if unit == "both" else res.cpu().numpy()
+
+    def _with_offsets(self, encode, text, unit):
+        """(ids, spans) as lists: one encode plus one spans call over its ids"""
+        if unit not in self._SPAN_UNITS:
+            raise ValueError(f"unit={unit!r} not understood: 'char', 'byte' or 'both'")
+        ids = encode(text)
+        res = self.token_spans(ids, unit=unit)
+        if unit == "both":
+            return ids, tuple(list(map(tuple, r.tolist())) for r in res)
+        return ids, list(map(tuple, res.tolist()))
+
     # -- fixed-length rows from ids that live in HBM (DESIGN 4.4) ---------------------
     def rows_resident(self, ids, doc_offsets, row_len, *, stride=None, sep=None, pad=0, mode="pack", truncate="right",
                       pad_side="right", dtype=None, drop_last=False, return_doc_index=False, return_positions=False,
@@ -491,6 +585,12 @@ class BasicTokenizer(Tokenizer):
         ids, _ = self._encode_chunks([text.encode("utf-8")])
         return ids.tolist()
 
+    def encode_with_offsets(self, text, unit="char"):
+        """(ids, spans): encode(text) and, for every token, its (start, end) in `text` -- in characters (unit="char":
+        text[start:end] covers the token), in bytes of text.encode("utf-8") (unit="byte"), or the pair of both lists
+        (unit="both").  One encode plus one token_spans call; not in the reference."""
+        return self._with_offsets(self.encode, text, unit)
+
 
 class RegexTokenizer(Tokenizer):
     """BPE over regex-split chunks with optional special tokens (regex.py:22-164)."""
@@ -577,6 +677,12 @@ class RegexTokenizer(Tokenizer):
     def encode_ordinary(self, text):
         data, offs = self._chunked(text)
         return self._encode_flat(data, offs)[0].tolist()
+
+    def encode_ordinary_with_offsets(self, text, unit="char"):
+        """(ids, spans): encode_ordinary(text) and, for every token, its (start, end) in `text` -- in characters
+        (unit="char": text[start:end] covers the token), in bytes of text.encode("utf-8") (unit="byte"), or the pair of
+        both lists (unit="both").  One encode plus one token_spans call; not in the reference."""
+        return self._with_offsets(self.encode_ordinary, text, unit)
 
     def encode_ordinary_batch(self, texts):
         """encode_ordinary() of every text, as one device batch (not in the reference, whose
