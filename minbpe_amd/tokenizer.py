@@ -46,7 +46,8 @@ def engine(device=None) -> "_native.Engine":
 
 def get_stats(ids, counts=None):
     """Adjacent-pair counts of `ids` as a dict in first-occurrence order;
-    accumulates into `counts` when given (base.py:13-22)."""
+    accumulates into `counts` when given (base.py:13-22).  Ids must be below 65535, the engine's
+    limit: a larger one raises RuntimeError naming that limit (there is no host path)."""
     counts = {} if counts is None else counts
     if len(ids) < 2:
         return counts
@@ -59,7 +60,8 @@ def get_stats(ids, counts=None):
 
 def merge(ids, pair, idx):
     """Replace every left-to-right non-overlapping occurrence of `pair` in `ids`
-    by `idx` (base.py:25-41)."""
+    by `idx` (base.py:25-41).  Ids, `pair` and `idx` must be below 65535, the engine's limit: a
+    larger one raises RuntimeError naming that limit (there is no host path)."""
     if len(ids) == 0:
         return []
     eng = engine()
