@@ -1406,12 +1406,14 @@ int launch_chain_step(bpe_ctx *c, uint32_t step, uint32_t zhi, bool use_index, b
     LAUNCHCHK(c, "k_merge_chain");
     TRY(prof_end(c));
     TRY(prof_begin(c, BPE_PROF_TABLE, 0));
-    const uint32_t na = (zhi + 1 + 255) / 256;
+    // (the table update: 64 tokens per workgroup, a wave per pair group -- four groups: a thread holds up to AW_PP pairs a
+    // turn, a batch of 31 is two turns; the committing workgroups are what they were)
+    const uint32_t na = (zhi + 1 + 63) / 64;
     const uint32_t ncommit = std::max(8u, std::min(128u, (nwords + 255) / 256));  // (a mask word per thread, at most)
     const uint32_t fS = std::min<uint32_t>(c->vcap, ((zhi + 1 + 63) / 64) * 64);  // vector stride of the SUM payload
     uint32_t *ftail = dp ? c->d_dp_cfold + (size_t)2 * kcap * fS : nullptr;
     if (dp) {
-        hipLaunchKernelGGL(GK(c, k_dp_fold_chain), dim3(na), dim3(256), 0, c->stream, c->d_delta, dl, c->d_st, c->d_dp_cfold, fS, ftail);
+        hipLaunchKernelGGL(GK(c, k_dp_fold_chain), dim3((zhi + 1 + 255) / 256), dim3(256), 0, c->stream, c->d_delta, dl, c->d_st, c->d_dp_cfold, fS, ftail);
         LAUNCHCHK(c, "k_dp_fold_chain");
         TRY(dp_allreduce(c, c->d_dp_cfold, (uint64_t)2 * kcap * fS + 64, BPE_DT_INT32, BPE_OP_SUM));
     }

@@ -644,7 +644,9 @@ struct MergeLds {
     alignas(8) uint2 s_ph[256];  // (the pairs' look-up table: chain_hash_build)
     uint32_t s_hm;
     uint32_t s_hs[512];  // (chain_hash_find's scratch)
+    uint32_t s_mk[LEAN_SUB];  // (a round's candidate masks, combined over the pair groups)
 };
+static_assert(LEAN_MT == 8 * (int)LEAN_SUB && CH_KMAX <= 32, "candidate masks: eight pair groups of at most four pairs");
 // (s_pa / s_pb are filled and a barrier has passed; every thread of the workgroup calls; THROUGH: k_step -- the
 // staged headers are committed by other workgroups of the same launch)
 template <bool THROUGH = false>
@@ -662,6 +664,7 @@ __device__ __forceinline__ void merge_chain_body(const AbArgs &A, const uint32_t
     auto &s_tot = L.s_tot;
     auto &s_pa = L.s_pa;
     auto &s_pb = L.s_pb;
+    if (threadIdx.x < LEAN_SUB) L.s_mk[threadIdx.x] = 0;  // (the barriers of chain_hash_build follow)
     const uint32_t hm = chain_hash_build(L.s_ph, &L.s_hm, L.s_hs, s_pa, s_pb, K, pre_ok, pre_hm);
     const uint2 *s_ph = L.s_ph;
     // (have_st: the caller fetched the state words this pass needs in one round trip with the batch)
@@ -701,16 +704,39 @@ __device__ __forceinline__ void merge_chain_body(const AbArgs &A, const uint32_t
     const uint32_t per = (nwords + nblk - 1) / nblk;  // mask words of one workgroup
     const uint32_t wlo = blk * per, whi = min(nwords, wlo + per);
     for (uint32_t sub = wlo; sub < whi; sub += LEAN_SUB) {
+        // the round's candidate masks: all 1024 threads take part -- thread tid holds mask word sub + (tid & 127) and the
+        // pairs p = tid >> 7 (mod 8), at most four of them, and has every index word of its pairs in flight before it
+        // looks at one: ONE round trip per round whatever K is (128 threads looping over the pairs were K / 2 dependent
+        // ones, with the other 896 threads waiting at the barrier).  The pair groups' masks of a word meet in s_mk, which
+        // its reader leaves zeroed for the next round (merge_chain_body's caller: zeroed before the first).
+        {
+            const uint32_t pg = threadIdx.x >> 7, wq = sub + (threadIdx.x & (LEAN_SUB - 1u));
+            uint32_t v[4][3];
+#pragma unroll
+            for (int j = 0; j < 4; j++) {
+                const uint32_t p = pg + 8u * (uint32_t)j;
+                v[j][0] = v[j][1] = v[j][2] = 0;
+                if (p < K && wq < whi) {
+                    uint32_t h1, h2, h3;
+                    pair_hash(s_pa[p], s_pb[p], h1, h2, h3);
+                    v[j][0] = A.idx[(size_t)h1 * A.istride + wq];
+                    v[j][1] = A.idx[(size_t)h2 * A.istride + wq];
+                    v[j][2] = A.idx[(size_t)h3 * A.istride + wq];
+                }
+            }
+            uint32_t pm = (pg == 0 && wq < whi) ? idx_dirty[wq] : 0u;
+#pragma unroll
+            for (int j = 0; j < 4; j++) pm |= v[j][0] & v[j][1] & v[j][2];
+            if (pm) atomicOr(&L.s_mk[threadIdx.x & (LEAN_SUB - 1u)], pm);
+        }
+        __syncthreads();
         uint32_t mk = 0;
         const uint32_t w = sub + threadIdx.x;
+        if (threadIdx.x < LEAN_SUB) {
+            mk = L.s_mk[threadIdx.x];
+            L.s_mk[threadIdx.x] = 0;
+        }
         if (threadIdx.x < LEAN_SUB && w < whi) {
-            mk = idx_dirty[w];
-            for (uint32_t p = 0; p < K; p++) {
-                uint32_t h1, h2, h3;
-                pair_hash(s_pa[p], s_pb[p], h1, h2, h3);
-                mk |= A.idx[(size_t)h1 * A.istride + w] & A.idx[(size_t)h2 * A.istride + w] &
-                      A.idx[(size_t)h3 * A.istride + w];
-            }
             if (aa) {
                 // build_cand_list's a == b rule (k_index.hip): the pass charges every pair to its LEFT element, so the slot
                 // before a candidate owes table updates too -- slot s is visited if s or s + 1 is a candidate or marked.
@@ -1027,7 +1053,9 @@ __device__ __forceinline__ void apply_chain_tokens(const uint32_t t, uint32_t *_
             flagged |= live && ((t == a) | (t == b) | (t == Z));
         } else {
             // ---- a batch: brep replicas per pair, eight pairs' worth of loads in flight at a time -------------------------
-            const uint32_t brep = folded ? 0u : brep_in;
+            // (k_apply_chain comes here with the sharded payload alone: its own replica blocks go through
+            // apply_chain_tokens_wide, below)
+            const uint32_t brep = (!OWNED || folded) ? 0u : brep_in;
             constexpr int G = OWNED ? 4 : 8;  // (k_step's workgroups are 1024 threads: 128 registers per lane, not 256)
             for (uint32_t g = 0; g < K; g += G) {  // (uniform)
                 uint32_t x[G][CH_REP][2];
@@ -1061,7 +1089,7 @@ __device__ __forceinline__ void apply_chain_tokens(const uint32_t t, uint32_t *_
                             sl += x[q][r][0];
                             sr += x[q][r][1];
                         }
-                    } else {  // (pairs with thousands of sites: all CH_RSTRIDE replicas, one pair at a time)
+                    } else if (OWNED) {  // (pairs with thousands of sites: all CH_RSTRIDE replicas, one pair at a time)
                         constexpr int YB = OWNED ? CH_RSTRIDE / 2 : CH_RSTRIDE;
 #pragma unroll
                         for (int r0 = 0; r0 < CH_RSTRIDE; r0 += YB) {
@@ -1116,6 +1144,112 @@ __device__ __forceinline__ void apply_chain_tokens(const uint32_t t, uint32_t *_
         const uint32_t arg = (uint32_t)__shfl((int)rm.y, fl);
         if (lane == 0) sums[gw] = make_uint4(m, base + (uint32_t)fl, arg, (uint32_t)__popcll(bal));
     }
+}
+// The batch branch above as k_apply_chain runs it (this rank's replica blocks, K > 1): a workgroup is 64 tokens (the lane)
+// times ng pair groups (the wave; the host launches four); group pg takes the pairs p = pg (mod ng), AW_PP of them a turn.
+// At CH_REP replicas per pair all of a turn's delta words are in flight together: one round trip up to 16 pairs, two up
+// to 31 (ceil(K / 8) before).  At CH_RSTRIDE a round is one pair's 32 words: ceil(K / ng) round trips (K before; two
+// pairs a round cost 147 registers a lane, one pair 112).  A row's flag needs every group's word: the groups' flags meet
+// in s_flag (64 words, zeroed, a barrier passed), and group 0 alone does the flag word and the 64-row record, as above.
+// Every thread of the workgroup calls.
+constexpr int AW_PP = 4;
+__device__ __forceinline__ void apply_chain_tokens_wide(const uint32_t t, const uint32_t pg, const uint32_t ng,
+                                                        uint32_t *__restrict__ mat, uint32_t stride, uint32_t *__restrict__ delta,
+                                                        uint32_t vcap, const uint32_t *__restrict__ rowmax,
+                                                        uint32_t *__restrict__ dbits, uint4 *__restrict__ sums, const uint32_t K,
+                                                        const uint32_t z0, const uint32_t *pairs, const uint32_t *adjs,
+                                                        const uint32_t brep, uint32_t *s_flag) {
+    const uint32_t Zlast = z0 + K - 1u;
+    if ((t & ~255u) > Zlast) return;  // (the host sized the grid for the most a step can reach; uniform: 64 | 256)
+    const bool live = t <= Zlast;     // (dead lanes stay for the wave reductions below)
+    const uint32_t vc = vcap & 0xFFFFFFu;
+    uint2 rm = make_uint2(0u, 0u);
+    uint32_t prevflag = 0;
+    if (live && (pg == 0 || pg < K)) {  // (a group without a pair only joins the barrier)
+        if (pg == 0) prevflag = (dbits[t >> 5] >> (t & 31)) & 1u;  // (flagged by an earlier step of this level, not re-scanned yet)
+        rm = reinterpret_cast<const uint2 *>(rowmax)[t];
+    }
+    bool flagged = false;
+    auto finish = [&](const uint32_t p, const uint32_t sl, const uint32_t sr) {  // (p < K)
+        const uint32_t a = pairs[p] >> 16, b = pairs[p] & 0xFFFFu, Z = z0 + p;
+        const uint32_t dr = sr + (t == a ? adjs[p] : 0u), ir = sr + (t == Z ? adjs[p] : 0u);
+        if (sl) {
+            // (the value before: decides whether row t's maximum may have moved.  Two pairs that share their first
+            // token may meet on (t, a) from two groups: whichever comes first sees the value that can equal the maximum)
+            const uint32_t old = atomicSub(&mat[(size_t)t * stride + a], sl);
+            atomicAdd(&mat[(size_t)t * stride + Z], sl);
+            flagged |= old == rm.x;
+        }
+        if (dr) atomicSub(&mat[(size_t)b * stride + t], dr);
+        if (ir) atomicAdd(&mat[(size_t)Z * stride + t], ir);
+        if (live && t == b) mat[(size_t)a * stride + b] = 0;
+        flagged |= live && ((t == a) | (t == b) | (t == Z));
+    };
+    if (brep == (uint32_t)CH_REP) {
+#pragma unroll 1
+        for (uint32_t g0 = pg; g0 < K; g0 += (uint32_t)AW_PP * ng) {  // (four groups: one turn up to 16 pairs)
+            uint32_t x[AW_PP][CH_REP][2];
+#pragma unroll
+            for (int j = 0; j < AW_PP; j++) {
+                const uint32_t p = g0 + (uint32_t)j * ng;
+#pragma unroll
+                for (int r = 0; r < CH_REP; r++) {
+                    const size_t o = delta_rep_off(p * (uint32_t)CH_RSTRIDE + (uint32_t)r, vc);
+                    x[j][r][0] = (live && p < K) ? delta[o + t] : 0u;
+                    x[j][r][1] = (live && p < K) ? delta[o + vc + t] : 0u;
+                }
+            }
+#pragma unroll
+            for (int j = 0; j < AW_PP; j++) {
+                const uint32_t p = g0 + (uint32_t)j * ng;
+                if (p >= K) break;  // (uniform in the wave)
+                uint32_t sl = 0, sr = 0;
+#pragma unroll
+                for (int r = 0; r < CH_REP; r++) {
+                    const size_t o = delta_rep_off(p * (uint32_t)CH_RSTRIDE + (uint32_t)r, vc);
+                    if (x[j][r][0]) delta[o + t] = 0;
+                    if (x[j][r][1]) delta[o + vc + t] = 0;
+                    sl += x[j][r][0];
+                    sr += x[j][r][1];
+                }
+                finish(p, sl, sr);
+            }
+        }
+    } else {  // (pairs with thousands of sites: all CH_RSTRIDE replicas, a pair at a time)
+#pragma unroll 1
+        for (uint32_t p = pg; p < K; p += ng) {
+            uint32_t y[CH_RSTRIDE][2];
+#pragma unroll
+            for (int r = 0; r < CH_RSTRIDE; r++) {
+                const size_t o = delta_rep_off(p * (uint32_t)CH_RSTRIDE + (uint32_t)r, vc);
+                y[r][0] = live ? delta[o + t] : 0u;
+                y[r][1] = live ? delta[o + vc + t] : 0u;
+            }
+            uint32_t sl = 0, sr = 0;
+#pragma unroll
+            for (int r = 0; r < CH_RSTRIDE; r++) {
+                const size_t o = delta_rep_off(p * (uint32_t)CH_RSTRIDE + (uint32_t)r, vc);
+                if (y[r][0]) delta[o + t] = 0;
+                if (y[r][1]) delta[o + vc + t] = 0;
+                sl += y[r][0];
+                sr += y[r][1];
+            }
+            finish(p, sl, sr);
+        }
+    }
+    if (flagged) s_flag[lane_id()] = 1u;
+    __syncthreads();
+    if (pg != 0) return;
+    flagged = s_flag[lane_id()] != 0;
+    if (flagged && !prevflag) atomicOr(&dbits[t >> 5], 1u << (t & 31));
+    // ---- what the next FULL selection needs (apply_chain_tokens)
+    const uint32_t vs = (!live || flagged || prevflag) ? 0u : rm.x;
+    const uint32_t gw = t >> 6, base = gw * 64u;
+    const uint32_t m = wave_umax_dpp(vs);
+    const unsigned long long bal = __ballot(m != 0 && vs == m);
+    const int fl = bal ? __ffsll((long long)bal) - 1 : 0;
+    const uint32_t arg = (uint32_t)__shfl((int)rm.y, fl);
+    if (lane_id() == 0) sums[gw] = make_uint4(m, base + (uint32_t)fl, arg, (uint32_t)__popcll(bal));
 }
 // the step's records (the first 64 threads of ONE workgroup call)
 // (k_step: the workgroup that SELECTED calls -- what the selection left in st is then its own workgroup's writes; the
@@ -1217,10 +1351,13 @@ __device__ __forceinline__ void apply_chain_commit(uint32_t first, uint32_t stp,
         }
     }
 }
-// Workgroups [0, na): one token per thread, every pair of the batch.  Workgroups [na, grid): commit the staged headers;
-// the first of them also makes the stream length, the iteration records of the step's merges, the step record, and the
-// next step's mode.
-__global__ void __launch_bounds__(256)
+// Workgroups [0, na): 64 tokens each -- a batch of this rank's own delta: a token per lane, a pair group per wave
+// (apply_chain_tokens_wide); a batch of one and the sharded payload: a token per thread of the first wave, the other
+// waves leave.  Workgroups [na, grid): commit the staged headers; the first of them also makes the stream length, the
+// iteration records of the step's merges, the step record, and the next step's mode.
+// (64 threads per pair group, APPLY_MT at most; the host launches four groups, 256 threads -- eight were not measured)
+constexpr int APPLY_MT = 512;
+__global__ void __launch_bounds__(APPLY_MT)
 k_apply_chain(uint32_t *__restrict__ mat, uint32_t stride, uint32_t *__restrict__ delta, uint32_t vcap,
               const uint32_t *__restrict__ rowmax, DevState *st, uint32_t *__restrict__ dbits, int par, IterRec *rec,
               StepRec *srec, uint32_t step, uint32_t na, SlotHdr *__restrict__ hdr_cur, const StageRec *__restrict__ stage,
@@ -1231,7 +1368,7 @@ k_apply_chain(uint32_t *__restrict__ mat, uint32_t stride, uint32_t *__restrict_
     // SL at folded[2p fS ..), SR at folded[(2p + 1) fS ..), its adj in ftail[p] -- instead of this rank's replica blocks
     // (sharded: ftail[16] = the number of ranks whose status was raised when they folded this step's delta -- a
     // failure inside any rank's merge pass stops every rank at this same merge)
-    __shared__ uint32_t s_w[SW_WORDS], s_pairs[CH_KMAX];
+    __shared__ uint32_t s_w[SW_WORDS], s_pairs[CH_KMAX], s_flag[64];
     step_words_fetch(st, s_w);
     const uint32_t remote = (folded && ftail[16] != 0) ? 1u : 0u;
     const uint32_t status = s_w[SW_STATUS] ? s_w[SW_STATUS] : (remote ? ST_INTERNAL : 0u), defer = s_w[SW_DEFER];
@@ -1241,9 +1378,16 @@ k_apply_chain(uint32_t *__restrict__ mat, uint32_t stride, uint32_t *__restrict_
         if (noop) return;
         if (threadIdx.x < CH_KMAX) s_pairs[threadIdx.x] = (s_w[threadIdx.x] << 16) | (s_w[SW_BB + threadIdx.x] & 0xFFFFu);
         if (threadIdx.x == 0 && K == 1) s_w[SW_BADJ] = s_w[SW_ADJ];  // (a batch of one: merge_ab_wave's adj word)
+        if (threadIdx.x < 64) s_flag[threadIdx.x] = 0;
         __syncthreads();
-        apply_chain_tokens<false>(blockIdx.x * 256u + threadIdx.x, mat, stride, delta, vcap, rowmax, dbits, sums, folded, fS,
-                                  ftail, K, z0, 0u, s_pairs, s_w + SW_BADJ, s_w[SW_BREP]);
+        const uint32_t t = blockIdx.x * 64u + (uint32_t)lane_id();
+        if (K > 1 && !folded)
+            // (the pair group as a scalar: the replica blocks of a wave's pairs are then scalar bases, a lane adds its token)
+            apply_chain_tokens_wide(t, (uint32_t)__builtin_amdgcn_readfirstlane(wave_id()), blockDim.x >> 6, mat, stride, delta, vcap, rowmax, dbits, sums, K, z0,
+                                    s_pairs, s_w + SW_BADJ, s_w[SW_BREP], s_flag);
+        else if (wave_id() == 0)
+            apply_chain_tokens<false>(t, mat, stride, delta, vcap, rowmax, dbits, sums, folded, fS, ftail, K, z0, 0u, s_pairs,
+                                      s_w + SW_BADJ, s_w[SW_BREP]);
         return;
     }
     if (blockIdx.x == na && threadIdx.x < 64) apply_chain_records(st, par, rec, srec, step, removed, K, noop, status, defer, remote, removed_aa);
