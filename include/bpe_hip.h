@@ -74,7 +74,9 @@ int bpe_set_stream(bpe_ctx *ctx, void *hip_stream);
  *   bpe_rows_resident's pack kernel: "rows_tile" (4096: output elements per workgroup tile, 64..65536, a multiple of
  *   4), "rows_stage" (1024: document starts a tile stages in LDS, 0..4096; a tile that holds more searches global
  *   memory instead, and 0 makes every tile do so -- the cross-check form);
- *   bpe_token_spans_resident's emit kernel: "spans_stage" (1024, 0..4096: the same for its tiles of 1024 tokens). */
+ *   bpe_token_spans_resident's emit kernel: "spans_stage" (1024, 0..4096: the same for its tiles of 1024 tokens);
+ *   bpe_project_resident's placement kernel: "proj_tile" (256: tokens per workgroup tile, 64..16384, a multiple of
+ *   64), "proj_window" (2048: ids of its LDS window, 64..8192, a multiple of 4). */
 int bpe_set_option(bpe_ctx *ctx, const char *name, int64_t value);
 
 /* ---- input ----------------------------------------------------------------- */
@@ -347,6 +349,47 @@ int bpe_token_spans_resident(bpe_ctx *ctx, const void *d_ids, int32_t id_width, 
                              int64_t *d_byte_spans, int64_t *d_char_spans,
                              uint64_t *n_bytes, uint64_t *n_chars,
                              uint64_t *bad_index, uint64_t *bad_doc);
+
+/* ---- projection onto a smaller vocabulary ---------------------------- */
+/* A tokenizer of 256 + M entries contains every smaller one: its first vocab_size - 256 merges are the tokenizer of
+ * vocab_size entries, and what that one makes of a text is what this one makes of it with every id >= vocab_size
+ * expanded into its two children, recursively (both apply ranks in increasing order).  Ids that live in HBM are
+ * projected there; every large buffer is ON THE DEVICE and owned by the caller.
+ *   bpe_project_set_merges   the merge list, kept until replaced: merges = a0, b0, a1, b1, ..., merge r makes id 256 + r
+ *                    and must have the shape training makes: 0 <= a, b < 256 + r, no pair twice.  pass_ids (special
+ *                    tokens): n_pass ids, strictly ascending, each < 0 or >= 256 + M; they are legal in the input and
+ *                    pass through unchanged.  BPE_E_ARG for a list of another shape
+ *   E(t)             [t] if 0 <= t < vocab_size or t is a pass id; E(a) + E(b) if vocab_size <= t < 256 + M and (a, b)
+ *                    is the pair of t
+ *   bpe_project_resident     out = E(t_0) + E(t_1) + ... for the n ids of d_ids
+ *   d_ids, id_width  n ids of 4 (int32) or 8 (int64) bytes, read in place, never written
+ *   vocab_size       256 <= vocab_size <= 256 + M, else BPE_E_ARG
+ *   d_doc_token_offsets   k token positions (each <= n; NULL with k = 0), validated on the device
+ *   d_out, out_cap   receives the ids, of the input's width; NULL / 0 = only count.  Must not overlap d_ids: the
+ *                    caller's contract
+ *   d_doc_out_offsets     k entries: the output position of each of those positions (position n: the total); written
+ *                    by a count-only call too
+ *   *n_out           ids of the output (set whenever the ids are valid, also on BPE_E_CAP)
+ *   *bad_index       first position whose id does not project (~0 if none)
+ * Any id E() does not define -- negative ids and 64-bit ids outside the int32 range included, unless a pass id -- fails
+ * with BPE_E_ARG and *bad_index, and nothing is written; out_cap < *n_out fails with BPE_E_CAP and writes nothing to
+ * d_out; a document position > n fails with BPE_E_ARG and writes nothing to d_out.  Never writes d_out[out_cap] or
+ * beyond, whatever the alignment of d_out (to id_width it must be aligned, as d_ids; 16-byte stores are used where the
+ * address allows).  BPE_E_STATE before bpe_project_set_merges.
+ * The expansions of one vocab_size -- length and ids of every id in [vocab_size, 256 + M) -- are a table made on the
+ * host from the merge list and uploaded by the first call at that size; the next calls at the same size build and
+ * upload nothing (one size is kept).  BPE_E_LIMIT, decided on the host from the merge list before any device work:
+ * the table would hold more than 2^28 ids (which also keeps every single expansion below 2^31), or n times the
+ * longest expansion reaches 2^62.
+ * Runs on the ctx's stream and synchronises it before returning; keeps no pointer of the caller's; only counters cross
+ * PCIe per call.  The decode vocab table is not touched.  The lengths and their scan are the ctx's decode scratch, shared
+ * with bpe_decode_batch: a result of that call not yet read is dropped. */
+int bpe_project_set_merges(bpe_ctx *ctx, const int32_t *merges, int32_t M,
+                           const int32_t *pass_ids, int32_t n_pass);
+int bpe_project_resident(bpe_ctx *ctx, const void *d_ids, int32_t id_width, uint64_t n, int32_t vocab_size,
+                         const uint64_t *d_doc_token_offsets, uint64_t k,
+                         void *d_out, uint64_t out_cap, uint64_t *d_doc_out_offsets,
+                         uint64_t *n_out, uint64_t *bad_index);
 
 /* ---- measurement ------------------------------------------------------------ */
 #define BPE_PROF_WIDEN 0

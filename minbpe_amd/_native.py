@@ -102,6 +102,9 @@ _SIGS = {
                                     _p, _p, _p, C.POINTER(_u64), C.POINTER(_u64)]),
     "bpe_token_spans_resident": (C.c_int, [_p, _p, _i32, _u64, _p, _u64, _p, _p, C.POINTER(_u64), C.POINTER(_u64),
                                            C.POINTER(_u64), C.POINTER(_u64)]),
+    "bpe_project_set_merges": (C.c_int, [_p, _p, _i32, _p, _i32]),
+    "bpe_project_resident": (C.c_int, [_p, _p, _i32, _u64, _i32, _p, _u64, _p, _u64, _p, C.POINTER(_u64),
+                                       C.POINTER(_u64)]),
     "bpe_prof_reset": (C.c_int, [_p]),
     "bpe_prof_read": (C.c_int, [_p, _p, _p, _p]),
     "bpe_encode_uses_16bit": (C.c_int, [_p, C.c_int32]),
@@ -621,6 +624,32 @@ class Engine:
             raise BadDocOffsets(int(bad_doc.value), (_lib.bpe_last_error(self._h) or b"").decode())
         self._check(rc)
         return int(nb.value), int(nc.value)
+
+    # -- projection onto a smaller vocabulary ------------------------------------------
+    def project_set_merges(self, pairs, pass_ids=()):
+        """bpe_project_set_merges: pairs [M, 2] int32 in merge order (merge r makes id 256 + r), pass_ids the ids outside
+        [0, 256 + M) that pass through unchanged (int32, strictly ascending).  A list that does not have the shape
+        training makes raises ValueError."""
+        pairs = np.ascontiguousarray(pairs, dtype=np.int32).reshape(-1, 2)
+        pas = np.ascontiguousarray(pass_ids, dtype=np.int32).reshape(-1)
+        self._check(_lib.bpe_project_set_merges(self._h, _ptr(pairs) if len(pairs) else None, len(pairs),
+                                                _ptr(pas) if len(pas) else None, len(pas)))
+
+    def project_resident(self, d_ids: int, id_width: int, n: int, vocab_size: int, d_doc_off: int = 0, k: int = 0,
+                         d_out: int = 0, out_cap: int = 0, d_ooff: int = 0) -> int:
+        """bpe_project_resident: d_ids (n ids of id_width = 4 or 8 bytes), d_doc_off (k uint64 token positions), d_out
+        (room for out_cap ids of the same width; 0 = only count), d_ooff (k uint64) are device addresses (e.g. torch
+        tensor.data_ptr()).  Returns the number of ids the batch projects to.  An id that does not project raises
+        InvalidToken(position); too little room raises OutputTooSmall."""
+        no, bad = _u64(0), _u64(0)
+        rc = _lib.bpe_project_resident(self._h, C.c_void_p(d_ids), id_width, n, int(vocab_size), C.c_void_p(d_doc_off), k,
+                                       C.c_void_p(d_out), out_cap, C.c_void_p(d_ooff), C.byref(no), C.byref(bad))
+        if rc == BPE_E_ARG and bad.value != 0xFFFFFFFFFFFFFFFF:
+            raise InvalidToken(int(bad.value))
+        if rc == BPE_E_CAP:
+            raise OutputTooSmall(int(no.value), (_lib.bpe_last_error(self._h) or b"").decode())
+        self._check(rc)
+        return int(no.value)
 
     # -- measurement ----------------------------------------------------------------
     def prof_reset(self):

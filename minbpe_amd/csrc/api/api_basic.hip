@@ -76,7 +76,8 @@ void bpe_destroy(bpe_ctx *c) {
     if (c->h_stage) (void)hipHostFree(c->h_stage);
     for (hipEvent_t ev : c->ev_stage)
         if (ev) (void)hipEventDestroy(ev);
-    for (void *p : {(void *)c->d_step_pub, (void *)c->d_step_bar, (void *)c->d_step_stamps, (void *)c->d_forced})
+    for (void *p : {(void *)c->d_step_pub, (void *)c->d_step_bar, (void *)c->d_step_stamps, (void *)c->d_forced,
+                    (void *)c->d_proj_pass, (void *)c->d_proj_tab, (void *)c->d_proj_toff})
         if (p) (void)hipFree(p);
     if (c->own_stream && c->stream) (void)hipStreamDestroy(c->stream);
     delete c;
@@ -171,6 +172,13 @@ int bpe_set_option(bpe_ctx *c, const char *name, int64_t value) {
     } else if (!strcmp(name, "spans_stage")) {
         if (value < 0 || value > SPANS_STAGE_MAX) return fail(c, BPE_E_ARG, "spans_stage: 0..%u document starts", SPANS_STAGE_MAX);
         c->spans_stage = (int)value;
+    } else if (!strcmp(name, "proj_tile")) {
+        if (value < 64 || value > 16384 || value % 64) return fail(c, BPE_E_ARG, "proj_tile: 64..16384 tokens, a multiple of 64");
+        c->proj_tile = (int)value;
+    } else if (!strcmp(name, "proj_window")) {
+        if (value < 64 || value > PROJ_WINDOW_MAX || value % 4)
+            return fail(c, BPE_E_ARG, "proj_window: 64..%u ids, a multiple of 4", PROJ_WINDOW_MAX);
+        c->proj_window = (int)value;
     } else if (!strcmp(name, "prof_stride")) {
         if (value < 1 || value > 1024) return fail(c, BPE_E_ARG, "prof_stride must be 1..1024");
         c->prof_stride = (int)value;

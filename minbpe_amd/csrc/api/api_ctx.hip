@@ -239,6 +239,18 @@ struct bpe_ctx {
     uint64_t cap_dec_meta = 0, cap_spn_n = 0, cap_spn_docs = 0;
     bool dec_meta_valid = false;
     int spans_stage = 1024;  // option "spans_stage": document starts a tile stages in LDS (0: every lane searches global memory, the cross-check form)
+    // bpe_project_resident (k_project.hip): the merge list as given (host), the sorted pass ids, and the expansion table of
+    // the vocab_size last asked for (grow-only): entry e = id proj_vs + e, ids d_proj_tab[d_proj_toff[e] .. d_proj_toff[e + 1])
+    std::vector<int32_t> proj_merges;
+    int32_t proj_M = -1;     // -1: no bpe_project_set_merges yet
+    int32_t *d_proj_pass = nullptr, *d_proj_tab = nullptr;
+    uint32_t *d_proj_toff = nullptr;
+    uint64_t cap_proj_pass = 0, cap_proj_tab = 0, cap_proj_toff = 0;
+    uint32_t proj_n_pass = 0;
+    int64_t proj_vs = -1;    // the vocab_size the table on the device was made for (-1: none)
+    uint64_t proj_maxlen = 1;  // ... and its longest expansion
+    int proj_tile = 256;     // option "proj_tile": tokens per workgroup tile of the placement
+    int proj_window = 2048;  // option "proj_window": ids of its LDS window
 
     int mode = 1;     // 0 recount | 1 delta
     int profile = 0;  // 0 off | 1 hipEvents around the merge pass | 2 around every kernel class

@@ -15,6 +15,20 @@ int upload_offsets(bpe_ctx *c, const uint64_t *chunk_offsets, uint64_t n_chunks)
     if (n_chunks) TRY(upload_h2d(c, c->d_offsets, chunk_offsets, n_chunks * sizeof(uint64_t)));
     return BPE_OK;
 }
+
+// A merge list of the shape training makes: merge r makes id 256 + r out of tokens defined before it, no pair twice
+// (what the replay below and bpe_project_set_merges both rely on)
+bool merges_training_shape(const int32_t *merges, int32_t M) {
+    std::vector<unsigned long long> seen;
+    seen.reserve((size_t)M);
+    for (int32_t r = 0; r < M; r++) {
+        const int32_t a = merges[2 * r], b = merges[2 * r + 1];
+        if (a < 0 || b < 0 || a >= 256 + r || b >= 256 + r) return false;
+        seen.push_back(((unsigned long long)(uint32_t)a << 32) | (uint32_t)b);
+    }
+    std::sort(seen.begin(), seen.end());
+    return std::adjacent_find(seen.begin(), seen.end()) == seen.end();
+}
 }  // namespace
 
 // 16-bit token / rank columns in k_encode_short: every rank (0xFFFF = "none") and every token id must fit.
@@ -79,21 +93,7 @@ int encode_batch_impl(bpe_ctx *c, const int32_t *merges, const int32_t *merge_id
     constexpr uint64_t REPLAY_MIN_BYTES = 1u << 20;
     if (!resident && n_chunks == 1 && chunk_offsets[0] == 0 && !merge_ids && c->enc_replay && M > 0 && n >= REPLAY_MIN_BYTES &&
         256 + (int64_t)M <= 65535 && !c->dp_active) {
-        bool shape = true;
-        {
-            std::vector<unsigned long long> seen;
-            seen.reserve((size_t)M);
-            for (int32_t r = 0; r < M && shape; r++) {
-                const int32_t a = merges[2 * r], b = merges[2 * r + 1];
-                shape = a >= 0 && b >= 0 && a < 256 + r && b < 256 + r;
-                seen.push_back(((unsigned long long)(uint32_t)a << 32) | (uint32_t)b);
-            }
-            if (shape) {
-                std::sort(seen.begin(), seen.end());
-                shape = std::adjacent_find(seen.begin(), seen.end()) == seen.end();
-            }
-        }
-        if (shape) {
+        if (merges_training_shape(merges, M)) {
             const int saved_mode = c->mode;
             c->mode = 1;
             int rc = bpe_load_bytes(c, bytes, n, nullptr, 0);

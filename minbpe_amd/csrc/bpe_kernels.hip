@@ -64,4 +64,5 @@
 #include "kernels/k_decode.hip"
 #include "kernels/k_rows.hip"
 #include "kernels/k_spans.hip"
+#include "kernels/k_project.hip"
 #include "kernels/k_util.hip"

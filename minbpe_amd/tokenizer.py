@@ -409,6 +409,139 @@ class Tokenizer:
             return ids, tuple(list(map(tuple, r.tolist())) for r in res)
         return ids, list(map(tuple, res.tolist()))
 
+    # -- what the same ids look like at a smaller vocabulary ---------------
+    def _project_table(self):
+        """The merge list for the device: (pairs [M, 2] int32 in id order, pass ids int32 ascending, special ids inside
+        [0, 256 + M)).  ValueError unless the list has the shape training makes: merge r makes id 256 + r out of ids
+        below 256 + r (a pair cannot occur twice: it is a dict key)."""
+        key = (self.merges, len(self.merges), tuple(sorted(self.special_tokens.values())))
+        cached = getattr(self, "_pj_cache", None)
+        if cached is None or cached[0][0] is not key[0] or cached[0][1:] != key[1:]:
+            items = sorted(self.merges.items(), key=lambda kv: kv[1])
+            M = len(items)
+            for r, ((a, b), idx) in enumerate(items):
+                if idx != 256 + r or not (0 <= a < 256 + r and 0 <= b < 256 + r):
+                    raise ValueError(f"merge {(a, b)} -> {idx} does not have the shape training makes: "
+                                     f"merge r makes id 256 + r out of ids below it")
+            pairs = np.array([p for p, _ in items], dtype=np.int32).reshape(-1, 2)
+            specials = key[2]
+            if any(not -2**31 <= i < 2**31 for i in specials):
+                raise ValueError("projection needs every special token id to fit int32")
+            pass_ids = np.array(sorted({i for i in specials if not 0 <= i < 256 + M}), dtype=np.int32)
+            self._pj_cache = (key, pairs, pass_ids, [i for i in specials if 0 <= i < 256 + M])
+        return self._pj_cache[1:]
+
+    def _project_args(self, vocab_size):
+        """_project_table() once vocab_size has been checked against it"""
+        pairs, pass_ids, inside = self._project_table()
+        top = 256 + len(pairs)
+        if isinstance(vocab_size, bool) or not isinstance(vocab_size, (int, np.integer)) or not 256 <= vocab_size <= top:
+            raise ValueError(f"vocab_size must be an integer in [256, {top}], not {vocab_size!r}")
+        clash = [i for i in inside if i >= vocab_size]
+        if clash:
+            raise ValueError(f"special token id {clash[0]} lies in [{vocab_size}, {top}): the tokenizer of {vocab_size} "
+                             f"entries reads it as a special token, the projection as a merge")
+        return pairs, pass_ids
+
+    def at_vocab(self, vocab_size):
+        """A new tokenizer of the same class with the first vocab_size - 256 merges, the matching vocab and the same
+        pattern and special tokens: the tokenizer project_resident() projects onto."""
+        self._project_args(vocab_size)
+        tok = type(self)()
+        tok.pattern = self.pattern
+        if hasattr(self, "compiled_pattern"):
+            tok.compiled_pattern = self.compiled_pattern
+        tok.merges = {pair: idx for pair, idx in self.merges.items() if idx < vocab_size}
+        tok.vocab = {idx: b for idx, b in self.vocab.items() if not vocab_size <= idx < 256 + len(self.merges)}
+        if hasattr(self, "inverse_special_tokens"):
+            tok.register_special_tokens(dict(self.special_tokens))
+        else:
+            tok.special_tokens = dict(self.special_tokens)
+        return tok
+
+    def project_resident(self, ids, vocab_size, doc_offsets=None, out=None):
+        """What at_vocab(vocab_size) makes of the text `ids` were made of, computed from the ids alone, on the device: every
+        id >= vocab_size is expanded into its two children until none is left (exact: both tokenizers apply merges in
+        increasing rank); special tokens pass through.  `ids` is a 1-D contiguous int32 or int64 torch tensor
+        on the GPU; returns (ids', doc_offsets'): a tensor of the same dtype there, and -- with doc_offsets, token
+        positions as a tensor on the GPU or anything np.asarray takes -- the int64 position of each in ids' (None
+        without).  out: a tensor like ids to project into (the view out[:total] is returned; ValueError if it is too
+        small); without it the batch is measured by a count-only call first.  Ids that do not project raise what
+        decode() raises, for the first such id.  Nothing but counters crosses PCIe."""
+        return self._project(ids, vocab_size, doc_offsets, out, False)
+
+    def projected_count(self, ids, vocab_size):
+        """len(project(ids, vocab_size)) without making the ids: the point of the compression curve at vocab_size.  ids: as
+        project_resident takes them, or a list / array of integers on the host."""
+        import torch
+        if not isinstance(ids, torch.Tensor):
+            self._project_args(vocab_size)
+            ids = self._host_ids(ids)
+        return self._project(ids, vocab_size, None, None, True)
+
+    def project(self, ids, vocab_size):
+        """project_resident() for ids on the host (a list or an array of integers): a list."""
+        self._project_args(vocab_size)
+        return self._project(self._host_ids(ids), vocab_size, None, None, False)[0].cpu().tolist()
+
+    @staticmethod
+    def _host_ids(ids):
+        arr = np.asarray(ids)
+        if arr.size and arr.dtype.kind not in "iu":
+            raise TypeError("token ids must be integers")
+        if arr.ndim > 1:
+            raise TypeError("token ids must be a flat list or a 1-D array")
+        import torch
+        arr = np.ascontiguousarray(arr.astype(np.int64, copy=False).reshape(-1))
+        return torch.from_numpy(arr).to(torch.device("cuda", _default_device()))
+
+    def _project(self, ids, vocab_size, doc_offsets, out, count_only):
+        import torch
+        if not isinstance(ids, torch.Tensor) or not ids.is_cuda or ids.dim() != 1 or not ids.is_contiguous() \
+                or ids.dtype not in (torch.int32, torch.int64):
+            raise TypeError("ids must be a 1-D contiguous int32 or int64 torch tensor on the GPU")
+        dev = ids.device
+        if out is not None and (not isinstance(out, torch.Tensor) or out.device != dev or out.dtype != ids.dtype
+                                or out.dim() != 1 or not out.is_contiguous()):
+            raise TypeError("out must be a 1-D contiguous torch tensor of the dtype and on the device of ids")
+        if doc_offsets is not None and isinstance(doc_offsets, torch.Tensor) \
+                and (doc_offsets.device != dev or doc_offsets.dtype not in (torch.int32, torch.int64)):
+            raise TypeError("doc_offsets must be an integer tensor on the device of ids")
+        pairs, pass_ids = self._project_args(vocab_size)
+        eng = engine(dev.index)
+        if getattr(eng, "_project_owner", None) is not pairs:  # (a new array whenever merges or special tokens changed)
+            eng.project_set_merges(pairs, pass_ids)
+            eng._project_owner = pairs
+        n, width = ids.numel(), ids.element_size()
+        doff, ooff, k = None, None, 0
+        if doc_offsets is not None:
+            if isinstance(doc_offsets, torch.Tensor):
+                doff = doc_offsets.to(torch.int64).contiguous().reshape(-1)
+            else:
+                doff = torch.from_numpy(np.ascontiguousarray(doc_offsets, dtype=np.int64).reshape(-1)).to(dev)
+            k = doff.numel()
+            ooff = torch.empty(k, dtype=torch.int64, device=dev)
+        torch.cuda.current_stream(dev).synchronize()  # the caller's pending writes to ids (and uploads above) are done
+
+        def call(dst, with_docs):
+            try:
+                return eng.project_resident(ids.data_ptr(), width, n, int(vocab_size), doff.data_ptr() if with_docs else 0,
+                                            k if with_docs else 0, 0 if dst is None else dst.data_ptr(),
+                                            0 if dst is None else dst.numel(), ooff.data_ptr() if with_docs else 0)
+            except _native.InvalidToken as e:
+                raise self._invalid_token(int(ids[e.args[0]].item())) from None
+            except _native.OutputTooSmall as e:
+                raise ValueError(f"out holds {dst.numel()} ids, the batch projects to {e.needed}") from None
+
+        if count_only:
+            return call(None, False)
+        if out is None:
+            out = torch.empty(call(None, False), dtype=ids.dtype, device=dev)
+        elif out.numel() == 0 and call(None, False):  # (no room at all is a count-only call to the library)
+            raise ValueError("out holds 0 ids")
+        total = call(out, k > 0)
+        return out[:total], ooff
+
     # -- fixed-length rows from ids that live in HBM (DESIGN 4.4) ---------------------
     def rows_resident(self, ids, doc_offsets, row_len, *, stride=None, sep=None, pad=0, mode="pack", truncate="right",
                       pad_side="right", dtype=None, drop_last=False, return_doc_index=False, return_positions=False,
@@ -854,6 +987,9 @@ class GPT4Tokenizer(RegexTokenizer):
 
     def train(self, text, vocab_size, verbose=False):
         raise NotImplementedError
+
+    def at_vocab(self, vocab_size):
+        raise NotImplementedError  # (as train(): a GPT4Tokenizer is cl100k_base, whole)
 
     def save(self, file_prefix):
         raise NotImplementedError("GPT4Tokenizer cannot be saved.")
