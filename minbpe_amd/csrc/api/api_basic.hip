@@ -45,7 +45,7 @@ int bpe_create(int device_id, bpe_ctx **out) {
                                  bpe::bpe_g4::IDX_H * 4)) != hipSuccess)
         return bail("hipFuncSetAttribute(dynamic LDS)", e);
     if ((e = hipMalloc((void **)&c->d_st, sizeof(DevState))) != hipSuccess) return bail("hipMalloc", e);
-    if ((e = hipMalloc((void **)&c->d_scratch, 8 * sizeof(unsigned long long))) != hipSuccess)
+    if ((e = hipMalloc((void **)&c->d_scratch, SCRATCH_WORDS * sizeof(unsigned long long))) != hipSuccess)
         return bail("hipMalloc", e);
     *out = c;
     return BPE_OK;
@@ -412,12 +412,12 @@ int bpe_get_stats(bpe_ctx *c, uint64_t *n_pairs_out) {
     TRY(clear_table(c));
     HIPCHK(c, hipMemsetAsync(c->d_first, 0xFF, (size_t)c->vcur * c->vcap * sizeof(uint32_t), c->stream));
     TRY(launch_pair_count(c, true));
-    HIPCHK(c, hipMemsetAsync(c->d_scratch, 0, sizeof(unsigned long long), c->stream));
+    HIPCHK(c, hipMemsetAsync(&c->d_scratch->count, 0, sizeof(unsigned long long), c->stream));
     hipLaunchKernelGGL(k_count_nonzero, dim3(c->vcur), dim3(256), 0, c->stream, c->d_mat, c->vcap,
-                       c->vcur, c->d_scratch);
+                       c->vcur, &c->d_scratch->count);
     LAUNCHCHK(c, "k_count_nonzero");
     unsigned long long np = 0;
-    HIPCHK(c, hipMemcpyAsync(&np, c->d_scratch, sizeof np, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(&np, &c->d_scratch->count, sizeof np, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     c->stats_valid = true;
     if (n_pairs_out) *n_pairs_out = np;
@@ -437,12 +437,12 @@ int bpe_read_stats(bpe_ctx *c, int32_t *a, int32_t *b, uint64_t *cnt, uint64_t *
     HIPCHK(c, tf.alloc(capn * 8));
     int32_t *da = ta.as<int32_t>(), *db = tb.as<int32_t>();
     unsigned long long *dc = tc.as<unsigned long long>(), *df = tf.as<unsigned long long>();
-    HIPCHK(c, hipMemsetAsync(c->d_scratch, 0, sizeof(unsigned long long), c->stream));
+    HIPCHK(c, hipMemsetAsync(&c->d_scratch->count, 0, sizeof(unsigned long long), c->stream));
     hipLaunchKernelGGL(k_dump_stats, dim3(c->vcur), dim3(256), 0, c->stream, c->d_mat, c->d_first,
-                       c->vcap, c->vcur, da, db, dc, df, (unsigned long long)cap, c->d_scratch);
+                       c->vcap, c->vcur, da, db, dc, df, (unsigned long long)cap, &c->d_scratch->count);
     LAUNCHCHK(c, "k_dump_stats");
     unsigned long long np = 0;
-    HIPCHK(c, hipMemcpyAsync(&np, c->d_scratch, sizeof np, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(&np, &c->d_scratch->count, sizeof np, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     int rc = BPE_OK;
     if (np > cap) {
@@ -527,15 +527,15 @@ int bpe_read_chunk_starts(bpe_ctx *c, uint64_t *out, uint64_t cap, uint64_t *n_o
     DevTmp t_out;
     HIPCHK(c, t_out.alloc((cap ? cap : 1) * 8));
     unsigned long long *d_out = t_out.as<unsigned long long>();
-    HIPCHK(c, hipMemsetAsync(c->d_scratch, 0, sizeof(unsigned long long), c->stream));
+    HIPCHK(c, hipMemsetAsync(&c->d_scratch->count, 0, sizeof(unsigned long long), c->stream));
     if (c->n) {
         hipLaunchKernelGGL(k_collect_starts, dim3(grid_for(c->n, 256, c->num_cus * 8)), dim3(256), 0,
                            c->stream, c->d_ids[c->par], c->n, d_out, (unsigned long long)cap,
-                           c->d_scratch);
+                           &c->d_scratch->count);
         LAUNCHCHK(c, "k_collect_starts");
     }
     unsigned long long ns = 0;
-    HIPCHK(c, hipMemcpyAsync(&ns, c->d_scratch, sizeof ns, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(&ns, &c->d_scratch->count, sizeof ns, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     int rc = BPE_OK;
     if (ns > cap) {

@@ -9,6 +9,36 @@ struct DpComm {
     int rank = 0, nranks = 1;
 };
 
+// The counter words a launch leaves for the host to read back (c->d_scratch): every user's words, laid over one buffer of
+// SCRATCH_WORDS words.  All work of a ctx is on one stream and no user keeps a word from one call to the next, so the
+// views of different calls overlap.  A new user takes a view of its own here, and with it the check below.
+constexpr int SCRATCH_WORDS = 8;  // what bpe_create allocates
+union ScratchWords {
+    // bpe_get_stats, bpe_read_stats, bpe_read_chunk_starts, spans_meta, the resident encode's offset check
+    unsigned long long count;
+    struct {  // resident_two_pass (bpe_decode_batch_resident, bpe_project_resident); bpe_decode_batch: the first two
+        unsigned long long bad, total, docbad;
+    } two_pass;
+    struct {  // bpe_token_spans_resident: read back as one block
+        unsigned long long bad, totals[2], docbad, ends[2];
+    } spans;
+    struct {  // bpe_rows_resident: read back as one block
+        unsigned long long bad, ends[2];
+    } rows;
+    struct {  // encode_batch_impl (min_rank and starts: the stream-wide rounds of its longest chunks)
+        unsigned long long nlong, total;
+        uint32_t min_rank, pad;
+        unsigned long long starts, nhuge;
+    } enc;
+    struct {  // slots_leave, slots2_leave: the stream's length, which nobody reads (k_scan_top wants a place for it)
+        unsigned long long other[3], total;
+    } slots;
+    struct {  // bpe_dp_table_ready (k_dp_table_join): the largest count that does not fit
+        unsigned long long other[5], over;
+    } dp;
+};
+static_assert(sizeof(ScratchWords) <= SCRATCH_WORDS * sizeof(unsigned long long), "a user's words lie past the buffer");
+
 struct bpe_ctx {
     int device = 0;
     int num_cus = 256;
@@ -57,7 +87,7 @@ struct bpe_ctx {
     uint64_t cap_tiles = 0;
     IterRec *h_rec = nullptr;  // pinned, device-visible
     int rec_cap = 0;
-    unsigned long long *d_scratch = nullptr;  // 2 x u64 cursor/counter
+    ScratchWords *d_scratch = nullptr;  // SCRATCH_WORDS x u64 counters, by the names above
     uint32_t *d_delta = nullptr;       // 4 x vcap: decL | decR | incL | incR
     uint32_t *d_dirty_list = nullptr;  // rows whose rowmax must be recomputed
     uint32_t *d_dirty_n = nullptr;
@@ -340,6 +370,11 @@ int dev_realloc(bpe_ctx *c, T *&p, size_t count) {
 }
 
 inline uint64_t ntiles_of(uint64_t n) { return (n + TILE - 1) / TILE; }
+inline uint64_t scan_tiles(uint64_t n) { return (n + SCAN_TILE - 1) / SCAN_TILE; }  // workgroups of a scan over n values
+
+// exclusive scan of a length column (api_resident.hip)
+int scan_lengths(bpe_ctx *c, const uint32_t *len, uint64_t n, unsigned long long *bsum, unsigned long long *off,
+                 unsigned long long *d_total);
 
 int ensure_ids(bpe_ctx *c, uint64_t n) {
     // capacity padded so every tile load (and the +1 halo word) is in bounds
@@ -862,15 +897,9 @@ int slots_enter(bpe_ctx *c) {
 int slots_leave(bpe_ctx *c) {
     const uint64_t T = c->slot_T;
     if (T) {
-        const uint64_t nb = (T + SCAN_TILE - 1) / SCAN_TILE;
         hipLaunchKernelGGL(k_slot_lens, dim3(grid_for(T, 256, c->num_cus * 4)), dim3(256), 0, c->stream,
                            c->d_meta[c->mq], T, c->d_slot_lens);
-        hipLaunchKernelGGL(k_scan_blocksum, dim3((unsigned)nb), dim3(256), 0, c->stream, c->d_slot_lens, T,
-                           c->d_slot_bsum);
-        hipLaunchKernelGGL(k_scan_top, dim3(1), dim3(1024), 0, c->stream, c->d_slot_bsum, nb,
-                           c->d_scratch + 3);
-        hipLaunchKernelGGL(k_scan_apply, dim3((unsigned)nb), dim3(256), 0, c->stream, c->d_slot_lens, T,
-                           c->d_slot_bsum, c->d_slot_off);
+        TRY(scan_lengths(c, c->d_slot_lens, T, c->d_slot_bsum, c->d_slot_off, &c->d_scratch->slots.total));
         hipLaunchKernelGGL(k_slot_compact, dim3((unsigned)T), dim3(256), 0, c->stream, c->d_ids[0],
                            c->d_ids[1], c->d_meta[c->mq], c->d_slot_off, c->d_ids2);
         LAUNCHCHK(c, "k_slot_compact");
@@ -972,15 +1001,9 @@ int slots2_enter(bpe_ctx *c) {
 int slots2_leave(bpe_ctx *c) {
     const uint64_t T = c->slot_T;
     if (T) {
-        const uint64_t nb = (T + SCAN_TILE - 1) / SCAN_TILE;
         hipLaunchKernelGGL(GK(c, k_slot2_lens), dim3(grid_for(T, 256, c->num_cus * 4)), dim3(256), 0, c->stream,
                            c->d_hdr2[c->mq], T, c->d_slot_lens);
-        hipLaunchKernelGGL(k_scan_blocksum, dim3((unsigned)nb), dim3(256), 0, c->stream, c->d_slot_lens, T,
-                           c->d_slot_bsum);
-        hipLaunchKernelGGL(k_scan_top, dim3(1), dim3(1024), 0, c->stream, c->d_slot_bsum, nb,
-                           c->d_scratch + 3);
-        hipLaunchKernelGGL(k_scan_apply, dim3((unsigned)nb), dim3(256), 0, c->stream, c->d_slot_lens, T,
-                           c->d_slot_bsum, c->d_slot_off);
+        TRY(scan_lengths(c, c->d_slot_lens, T, c->d_slot_bsum, c->d_slot_off, &c->d_scratch->slots.total));
         hipLaunchKernelGGL(GK(c, k_slot2_compact), dim3((unsigned)((T + 3) / 4)), dim3(256), 0, c->stream, c->d_ids[0],
                            c->d_ids[1], c->d_hdr2[c->mq], T, c->d_slot_off, c->d_ids2);
         LAUNCHCHK(c, "k_slot2_compact");

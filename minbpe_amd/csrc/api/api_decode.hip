@@ -80,30 +80,18 @@ extern "C" int bpe_decode_batch(bpe_ctx *c, const int32_t *ids, uint64_t n, uint
         return BPE_OK;
     }
     HIPCHK(c, hipSetDevice(c->device));
-    const uint64_t nb = (n + SCAN_TILE - 1) / SCAN_TILE;
-    if (n > c->cap_dec_n) {
-        TRY(dev_realloc(c, c->d_dec_ids, (size_t)n));
-        TRY(dev_realloc(c, c->d_dec_len, (size_t)n));
-        TRY(dev_realloc(c, c->d_dec_off, (size_t)n + 1));
-        TRY(dev_realloc(c, c->d_dec_bsum, (size_t)nb + 1));
-        c->cap_dec_n = n;
-    }
-    unsigned long long *d_bad = c->d_scratch, *d_total = c->d_scratch + 1;
+    TRY(ensure_dec_scratch(c, n));
+    auto *w = &c->d_scratch->two_pass;
     HIPCHK(c, hipMemcpyAsync(c->d_dec_ids, ids, n * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipMemsetAsync(d_bad, 0xFF, sizeof(unsigned long long), c->stream));
+    HIPCHK(c, hipMemsetAsync(&w->bad, 0xFF, sizeof(unsigned long long), c->stream));
     TRY(prof_begin(c, BPE_PROF_DECODE, 4 * n));
     hipLaunchKernelGGL(k_decode_len, dim3(grid_for(n, 256, c->num_cus * 8)), dim3(256), 0, c->stream,
-                       c->d_dec_ids, n, c->d_dec_voff, c->dec_V, c->d_dec_len, d_bad);
+                       c->d_dec_ids, n, c->d_dec_voff, c->dec_V, c->d_dec_len, &w->bad);
     LAUNCHCHK(c, "k_decode_len");
-    hipLaunchKernelGGL(k_scan_blocksum, dim3((unsigned)nb), dim3(256), 0, c->stream, c->d_dec_len, n,
-                       c->d_dec_bsum);
-    hipLaunchKernelGGL(k_scan_top, dim3(1), dim3(1024), 0, c->stream, c->d_dec_bsum, nb, d_total);
-    hipLaunchKernelGGL(k_scan_apply, dim3((unsigned)nb), dim3(256), 0, c->stream, c->d_dec_len, n,
-                       c->d_dec_bsum, c->d_dec_off);
-    LAUNCHCHK(c, "k_scan_*");
+    TRY(scan_lengths(c, c->d_dec_len, n, c->d_dec_bsum, c->d_dec_off, &w->total));
     TRY(prof_end(c));
     unsigned long long hb[2] = {0, 0};  // {first bad position, total bytes}
-    HIPCHK(c, hipMemcpyAsync(hb, c->d_scratch, sizeof hb, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(hb, &w->bad, sizeof hb, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     if (hb[0] != ~0ull) {
         if (bad_index) *bad_index = hb[0];
@@ -174,82 +162,33 @@ extern "C" int bpe_decode_batch_resident(bpe_ctx *c, const void *d_ids, int32_t 
     if (n_bytes) *n_bytes = 0;
     if (bad_index) *bad_index = ~0ull;
     HIPCHK(c, hipSetDevice(c->device));
-    c->dec_have_result = false;
-    const uint64_t nb = (n + SCAN_TILE - 1) / SCAN_TILE;
-    if (n > c->cap_dec_n) {
-        TRY(dev_realloc(c, c->d_dec_ids, (size_t)n));
-        TRY(dev_realloc(c, c->d_dec_len, (size_t)n));
-        TRY(dev_realloc(c, c->d_dec_off, (size_t)n + 1));
-        TRY(dev_realloc(c, c->d_dec_bsum, (size_t)nb + 1));
-        c->cap_dec_n = n;
-    }
-    unsigned long long *d_bad = c->d_scratch, *d_total = c->d_scratch + 1, *d_docbad = c->d_scratch + 2;
-    uint32_t *d_tidx = (uint32_t *)c->d_dec_ids;
-    HIPCHK(c, hipMemsetAsync(d_bad, 0xFF, 3 * sizeof(unsigned long long), c->stream));
-    if (n == 0) {
-        HIPCHK(c, hipMemsetAsync(d_total, 0, sizeof(unsigned long long), c->stream));
-    } else {
-        TRY(prof_begin(c, BPE_PROF_DECODE, (uint64_t)id_width * n));
-        const dim3 grid(grid_for(n, 256, c->num_cus * 8));
-        if (id_width == 4)
-            hipLaunchKernelGGL(k_decode_res_len<int32_t>, grid, dim3(256), 0, c->stream, (const int32_t *)d_ids, n,
-                               c->d_dec_voff, c->dec_V_dense, c->d_dec_sparse, c->dec_n_sparse, d_tidx, c->d_dec_len, d_bad);
-        else
-            hipLaunchKernelGGL(k_decode_res_len<int64_t>, grid, dim3(256), 0, c->stream, (const int64_t *)d_ids, n,
-                               c->d_dec_voff, c->dec_V_dense, c->d_dec_sparse, c->dec_n_sparse, d_tidx, c->d_dec_len, d_bad);
+    const TwoPassText txt = {"invalid token id at position %llu", "bytes", 0, 1};
+    auto len = [&](unsigned long long *d_bad) -> int {  // also the table index of every id, into d_dec_ids
+        by_width(id_width, [&](auto t) {
+            using T = decltype(t);
+            hipLaunchKernelGGL(k_decode_res_len<T>, dim3(grid_for(n, 256, c->num_cus * 8)), dim3(256), 0, c->stream,
+                               (const T *)d_ids, n, c->d_dec_voff, c->dec_V_dense, c->d_dec_sparse, c->dec_n_sparse,
+                               (uint32_t *)c->d_dec_ids, c->d_dec_len, d_bad);
+        });
         LAUNCHCHK(c, "k_decode_res_len");
-        hipLaunchKernelGGL(k_scan_blocksum, dim3((unsigned)nb), dim3(256), 0, c->stream, c->d_dec_len, n, c->d_dec_bsum);
-        hipLaunchKernelGGL(k_scan_top, dim3(1), dim3(1024), 0, c->stream, c->d_dec_bsum, nb, d_total);
-        hipLaunchKernelGGL(k_scan_apply, dim3((unsigned)nb), dim3(256), 0, c->stream, c->d_dec_len, n, c->d_dec_bsum,
-                           c->d_dec_off);
-        LAUNCHCHK(c, "k_scan_*");
-        TRY(prof_end(c));
-    }
-    unsigned long long hb[3] = {0, 0, 0};  // {first bad position, total bytes, first bad document entry}
-    HIPCHK(c, hipMemcpyAsync(hb, c->d_scratch, 2 * sizeof(unsigned long long), hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    if (hb[0] != ~0ull) {
-        if (bad_index) *bad_index = hb[0];
-        TRY(prof_drain(c));
-        return fail(c, BPE_E_ARG, "invalid token id at position %llu", hb[0]);
-    }
-    const uint64_t total = hb[1];
-    if (n_bytes) *n_bytes = total;
-    if (k) {
-        hipLaunchKernelGGL(k_decode_doc_offsets, dim3((unsigned)((k + 255) / 256)), dim3(256), 0, c->stream, c->d_dec_off, n,
-                           (unsigned long long)total, (const unsigned long long *)d_doc_token_offsets, k,
-                           (unsigned long long *)d_doc_byte_offsets, d_docbad);
-        LAUNCHCHK(c, "k_decode_doc_offsets");
-        HIPCHK(c, hipMemcpyAsync(hb + 2, d_docbad, sizeof(unsigned long long), hipMemcpyDeviceToHost, c->stream));
-        HIPCHK(c, hipStreamSynchronize(c->stream));
-        if (hb[2] != ~0ull) {
-            TRY(prof_drain(c));
-            return fail(c, BPE_E_ARG, "doc_token_offsets[%llu] is past the last token", hb[2]);
-        }
-    }
-    if (!d_out || out_cap == 0 || total == 0) {  // only count (or nothing to write)
-        TRY(prof_drain(c));
         return BPE_OK;
-    }
-    if (out_cap < total) {
-        TRY(prof_drain(c));
-        return fail(c, BPE_E_CAP, "need %llu bytes", (unsigned long long)total);
-    }
-    TRY(prof_begin(c, BPE_PROF_DECODE, total));
-    if (c->dec_copy) {
-        const uint64_t ntiles = (n + (uint64_t)c->dec_tile - 1) / (uint64_t)c->dec_tile;
-        const unsigned grid = (unsigned)std::min<uint64_t>(ntiles, (uint64_t)c->num_cus * 64);
-        hipLaunchKernelGGL(k_decode_copy_staged, dim3(grid), dim3(256), (size_t)c->dec_window, c->stream, d_tidx, n,
-                           c->d_dec_voff, c->d_dec_blob, c->d_dec_off, (unsigned long long)total, d_out,
-                           (uint32_t)c->dec_tile, (uint32_t)c->dec_window);
-        LAUNCHCHK(c, "k_decode_copy_staged");
-    } else {  // one token per lane over the resolved indices (every one is a table index: the check passes)
-        hipLaunchKernelGGL(k_decode_copy, dim3(grid_for(n, 256, c->num_cus * 8)), dim3(256), 0, c->stream,
-                           (const int32_t *)d_tidx, n, c->d_dec_voff, c->dec_V, c->d_dec_blob, c->d_dec_off, d_out);
-        LAUNCHCHK(c, "k_decode_copy");
-    }
-    TRY(prof_end(c));
-    TRY(prof_drain(c));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    return BPE_OK;
+    };
+    auto place = [&](uint64_t total) -> int {
+        uint32_t *d_tidx = (uint32_t *)c->d_dec_ids;
+        if (c->dec_copy) {
+            const uint64_t ntiles = (n + (uint64_t)c->dec_tile - 1) / (uint64_t)c->dec_tile;
+            const unsigned grid = (unsigned)std::min<uint64_t>(ntiles, (uint64_t)c->num_cus * 64);
+            hipLaunchKernelGGL(k_decode_copy_staged, dim3(grid), dim3(256), (size_t)c->dec_window, c->stream, d_tidx, n,
+                               c->d_dec_voff, c->d_dec_blob, c->d_dec_off, (unsigned long long)total, d_out,
+                               (uint32_t)c->dec_tile, (uint32_t)c->dec_window);
+            LAUNCHCHK(c, "k_decode_copy_staged");
+        } else {  // one token per lane over the resolved indices (every one is a table index: the check passes)
+            hipLaunchKernelGGL(k_decode_copy, dim3(grid_for(n, 256, c->num_cus * 8)), dim3(256), 0, c->stream,
+                               (const int32_t *)d_tidx, n, c->d_dec_voff, c->dec_V, c->d_dec_blob, c->d_dec_off, d_out);
+            LAUNCHCHK(c, "k_decode_copy");
+        }
+        return BPE_OK;
+    };
+    return resident_two_pass(c, id_width, n, d_doc_token_offsets, k, d_doc_byte_offsets, d_out, out_cap, n_bytes, bad_index,
+                             txt, len, place);
 }

@@ -62,11 +62,12 @@ extern "C" int bpe_dp_table_ready(bpe_ctx *c) {
     HIPCHK(c, hipSetDevice(c->device));
     // the GLOBAL counts from the summed limbs; a pair that occurs 2^32 times or more in the whole job does not fit the
     // 32-bit table -- every rank sees the same sums, so every rank fails here, before any further collective
-    HIPCHK(c, hipMemsetAsync(c->d_scratch + 5, 0, sizeof(unsigned long long), c->stream));
-    hipLaunchKernelGGL(k_dp_table_join, dim3(256), dim3(256), 0, c->stream, c->d_dp_table, c->d_mat, c->vcap, c->d_scratch + 5);
+    unsigned long long *d_over = &c->d_scratch->dp.over;
+    HIPCHK(c, hipMemsetAsync(d_over, 0, sizeof(unsigned long long), c->stream));
+    hipLaunchKernelGGL(k_dp_table_join, dim3(256), dim3(256), 0, c->stream, c->d_dp_table, c->d_mat, c->vcap, d_over);
     LAUNCHCHK(c, "k_dp_table_join");
     unsigned long long over = 0;
-    HIPCHK(c, hipMemcpyAsync(&over, c->d_scratch + 5, sizeof over, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(&over, d_over, sizeof over, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     if (over)
         return fail(c, BPE_E_LIMIT, "a byte pair occurs %llu times in the %d shards together: counts are 32-bit "

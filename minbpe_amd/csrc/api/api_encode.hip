@@ -76,11 +76,12 @@ int encode_batch_impl(bpe_ctx *c, const int32_t *merges, const int32_t *merge_id
     }
     HIPCHK(c, hipSetDevice(c->device));
     if (resident) {  // (the host form validates its offsets on the host)
-        HIPCHK(c, hipMemsetAsync(c->d_scratch, 0xFF, 8, c->stream));
+        unsigned long long *d_bad = &c->d_scratch->count;
+        HIPCHK(c, hipMemsetAsync(d_bad, 0xFF, 8, c->stream));
         hipLaunchKernelGGL(k_check_offsets, dim3(grid_for(n_chunks, 256, c->num_cus * 8)), dim3(256), 0, c->stream, chunk_offsets,
-                           n_chunks, n, c->d_scratch);
+                           n_chunks, n, d_bad);
         unsigned long long bad = 0;
-        HIPCHK(c, hipMemcpyAsync(&bad, c->d_scratch, 8, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipMemcpyAsync(&bad, d_bad, 8, hipMemcpyDeviceToHost, c->stream));
         HIPCHK(c, hipStreamSynchronize(c->stream));
         if (bad != ~0ull)
             return fail(c, BPE_E_ARG, "chunk_offsets[%llu]: offsets must ascend and stay <= n = %llu", bad, (unsigned long long)n);
@@ -185,7 +186,7 @@ int encode_batch_impl(bpe_ctx *c, const int32_t *merges, const int32_t *merge_id
         TRY(dev_realloc(c, c->d_enc_huge, (size_t)(n / (ENC_LONG_MAX + 1) + 2)));
         c->cap_enc_n = n;
     }
-    const uint64_t nb = (n_chunks + SCAN_TILE - 1) / SCAN_TILE;
+    const uint64_t nb = scan_tiles(n_chunks);
     if (n_chunks > c->cap_enc_chunks) {
         TRY(dev_realloc(c, c->d_enc_len, (size_t)n_chunks));
         TRY(dev_realloc(c, c->d_enc_off, (size_t)n_chunks + 1));
@@ -213,9 +214,10 @@ int encode_batch_impl(bpe_ctx *c, const int32_t *merges, const int32_t *merge_id
                            tslots);
         LAUNCHCHK(c, "k_enc_tab_init");
     }
-    unsigned long long *d_nlong = c->d_scratch, *d_total = c->d_scratch + 1, *d_nhuge = c->d_scratch + 4;
-    uint32_t *d_min = (uint32_t *)(c->d_scratch + 2);
-    HIPCHK(c, hipMemsetAsync(c->d_scratch, 0, 2 * sizeof(unsigned long long), c->stream));
+    auto *w = &c->d_scratch->enc;
+    unsigned long long *d_nlong = &w->nlong, *d_total = &w->total, *d_nhuge = &w->nhuge;
+    uint32_t *d_min = &w->min_rank;
+    HIPCHK(c, hipMemsetAsync(d_nlong, 0, 2 * sizeof(unsigned long long), c->stream));  // nlong, total
     HIPCHK(c, hipMemsetAsync(d_nhuge, 0, sizeof(unsigned long long), c->stream));
     const uint32_t mask = (uint32_t)(hs - 1);
     // 4. one chunk per lane -- with the cache, one DISTINCT chunk per lane
@@ -336,10 +338,10 @@ int encode_batch_impl(bpe_ctx *c, const int32_t *merges, const int32_t *merge_id
             c->n = stt.n[c->par];
         }
         if (rc_long == BPE_OK) {
-            HIPCHK(c, hipMemsetAsync(c->d_scratch + 3, 0, 8, c->stream));
+            HIPCHK(c, hipMemsetAsync(&w->starts, 0, 8, c->stream));
             hipLaunchKernelGGL(k_collect_starts, dim3(grid_for(c->n, 256, c->num_cus * 8)), dim3(256), 0,
                                c->stream, c->d_ids[c->par], c->n, d_starts, (unsigned long long)n_long,
-                               c->d_scratch + 3);
+                               &w->starts);
             std::vector<unsigned long long> starts(n_long + 1);
             HIPCHK(c, hipMemcpyAsync(starts.data(), d_starts, n_long * 8, hipMemcpyDeviceToHost, c->stream));
             HIPCHK(c, hipStreamSynchronize(c->stream));
@@ -373,11 +375,7 @@ int encode_batch_impl(bpe_ctx *c, const int32_t *merges, const int32_t *merge_id
                                c->d_enc_tab, c->d_enc_rep, c->d_enc_len, c->d_enc_bsum, d_ooff, n_chunks, d_out);
         }
     } else {
-        hipLaunchKernelGGL(k_scan_blocksum, dim3((unsigned)nb), dim3(256), 0, c->stream, c->d_enc_len, n_chunks,
-                           c->d_enc_bsum);
-        hipLaunchKernelGGL(k_scan_top, dim3(1), dim3(1024), 0, c->stream, c->d_enc_bsum, nb, d_total);
-        hipLaunchKernelGGL(k_scan_apply, dim3((unsigned)nb), dim3(256), 0, c->stream, c->d_enc_len, n_chunks,
-                           c->d_enc_bsum, d_ooff);
+        TRY(scan_lengths(c, c->d_enc_len, n_chunks, c->d_enc_bsum, d_ooff, d_total));
         hipLaunchKernelGGL(k_encode_place, dim3((unsigned)((n_chunks + 255) / 256)), dim3(256), 0, c->stream,
                            c->d_enc_tmp, d_offs, c->d_enc_len, d_ooff, n_chunks, d_out);
     }

@@ -119,80 +119,29 @@ extern "C" int bpe_project_resident(bpe_ctx *c, const void *d_ids, int32_t id_wi
         c->proj_vs = vocab_size;
         c->proj_maxlen = maxlen;
     }
-    c->dec_have_result = false;
-    const uint64_t nb = (n + SCAN_TILE - 1) / SCAN_TILE;
-    if (n > c->cap_dec_n) {  // (as bpe_decode_batch_resident grows it)
-        TRY(dev_realloc(c, c->d_dec_ids, (size_t)n));
-        TRY(dev_realloc(c, c->d_dec_len, (size_t)n));
-        TRY(dev_realloc(c, c->d_dec_off, (size_t)n + 1));
-        TRY(dev_realloc(c, c->d_dec_bsum, (size_t)nb + 1));
-        c->cap_dec_n = n;
-    }
     const uint32_t vs = (uint32_t)vocab_size, hi = 256u + (uint32_t)c->proj_M;
-    unsigned long long *d_bad = c->d_scratch, *d_total = c->d_scratch + 1, *d_docbad = c->d_scratch + 2;
-    HIPCHK(c, hipMemsetAsync(d_bad, 0xFF, 3 * sizeof(unsigned long long), c->stream));
-    if (n == 0) {
-        HIPCHK(c, hipMemsetAsync(d_total, 0, sizeof(unsigned long long), c->stream));
-    } else {
-        TRY(prof_begin(c, BPE_PROF_DECODE, (uint64_t)id_width * n));
-        const dim3 grid(grid_for(n, 256, c->num_cus * 8));
-        if (id_width == 4)
-            hipLaunchKernelGGL(k_project_len<int32_t>, grid, dim3(256), 0, c->stream, (const int32_t *)d_ids, n, vs, hi,
-                               c->d_proj_toff, c->d_proj_pass, c->proj_n_pass, c->d_dec_len, d_bad);
-        else
-            hipLaunchKernelGGL(k_project_len<int64_t>, grid, dim3(256), 0, c->stream, (const int64_t *)d_ids, n, vs, hi,
-                               c->d_proj_toff, c->d_proj_pass, c->proj_n_pass, c->d_dec_len, d_bad);
+    const TwoPassText txt = {"token id at position %llu does not project", "ids", (uint64_t)id_width, (uint64_t)id_width};
+    auto len = [&](unsigned long long *d_bad) -> int {
+        by_width(id_width, [&](auto t) {
+            using T = decltype(t);
+            hipLaunchKernelGGL(k_project_len<T>, dim3(grid_for(n, 256, c->num_cus * 8)), dim3(256), 0, c->stream,
+                               (const T *)d_ids, n, vs, hi, c->d_proj_toff, c->d_proj_pass, c->proj_n_pass, c->d_dec_len, d_bad);
+        });
         LAUNCHCHK(c, "k_project_len");
-        hipLaunchKernelGGL(k_scan_blocksum, dim3((unsigned)nb), dim3(256), 0, c->stream, c->d_dec_len, n, c->d_dec_bsum);
-        hipLaunchKernelGGL(k_scan_top, dim3(1), dim3(1024), 0, c->stream, c->d_dec_bsum, nb, d_total);
-        hipLaunchKernelGGL(k_scan_apply, dim3((unsigned)nb), dim3(256), 0, c->stream, c->d_dec_len, n, c->d_dec_bsum,
-                           c->d_dec_off);
-        LAUNCHCHK(c, "k_scan_*");
-        TRY(prof_end(c));
-    }
-    unsigned long long hb[3] = {0, 0, 0};  // {first bad position, total ids, first bad document entry}
-    HIPCHK(c, hipMemcpyAsync(hb, c->d_scratch, 2 * sizeof(unsigned long long), hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    if (hb[0] != ~0ull) {  // nothing has been written to the caller's buffers
-        if (bad_index) *bad_index = hb[0];
-        TRY(prof_drain(c));
-        return fail(c, BPE_E_ARG, "token id at position %llu does not project", hb[0]);
-    }
-    const uint64_t total = hb[1];
-    if (n_out) *n_out = total;
-    if (k) {
-        hipLaunchKernelGGL(k_decode_doc_offsets, dim3((unsigned)((k + 255) / 256)), dim3(256), 0, c->stream, c->d_dec_off, n,
-                           (unsigned long long)total, (const unsigned long long *)d_doc_token_offsets, k,
-                           (unsigned long long *)d_doc_out_offsets, d_docbad);
-        LAUNCHCHK(c, "k_decode_doc_offsets");
-        HIPCHK(c, hipMemcpyAsync(hb + 2, d_docbad, sizeof(unsigned long long), hipMemcpyDeviceToHost, c->stream));
-        HIPCHK(c, hipStreamSynchronize(c->stream));
-        if (hb[2] != ~0ull) {
-            TRY(prof_drain(c));
-            return fail(c, BPE_E_ARG, "doc_token_offsets[%llu] is past the last token", hb[2]);
-        }
-    }
-    if (!d_out || out_cap == 0 || total == 0) {  // only count (or nothing to write)
-        TRY(prof_drain(c));
         return BPE_OK;
-    }
-    if (out_cap < total) {
-        TRY(prof_drain(c));
-        return fail(c, BPE_E_CAP, "need %llu ids", (unsigned long long)total);
-    }
-    TRY(prof_begin(c, BPE_PROF_DECODE, (uint64_t)id_width * (n + total)));
-    const uint32_t tile = (uint32_t)c->proj_tile, W = (uint32_t)c->proj_window;
-    const uint64_t group = (uint64_t)PROJ_GROUP * tile, ngroups = (n + group - 1) / group;  // a workgroup takes PROJ_GROUP tiles at a time
-    const dim3 grid((unsigned)std::min<uint64_t>(ngroups, (uint64_t)c->num_cus * 32));
-    if (id_width == 4)
-        hipLaunchKernelGGL(k_project_place<int32_t>, grid, dim3(256), proj_lds_bytes(W), c->stream, (const int32_t *)d_ids, n, vs,
-                           hi, c->d_proj_toff, c->d_proj_tab, c->d_dec_off, (unsigned long long)total, (int32_t *)d_out, tile, W);
-    else
-        hipLaunchKernelGGL(k_project_place<int64_t>, grid, dim3(256), proj_lds_bytes(W), c->stream, (const int64_t *)d_ids, n, vs,
-                           hi, c->d_proj_toff, c->d_proj_tab, c->d_dec_off, (unsigned long long)total, (int64_t *)d_out, tile, W);
-    LAUNCHCHK(c, "k_project_place");
-    TRY(prof_end(c));
-    TRY(prof_drain(c));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    return BPE_OK;
+    };
+    auto place = [&](uint64_t total) -> int {
+        const uint32_t tile = (uint32_t)c->proj_tile, W = (uint32_t)c->proj_window;
+        const uint64_t group = (uint64_t)PROJ_GROUP * tile, ngroups = (n + group - 1) / group;  // a workgroup takes PROJ_GROUP tiles at a time
+        const dim3 grid((unsigned)std::min<uint64_t>(ngroups, (uint64_t)c->num_cus * 32));
+        by_width(id_width, [&](auto t) {
+            using T = decltype(t);
+            hipLaunchKernelGGL(k_project_place<T>, grid, dim3(256), proj_lds_bytes(W), c->stream, (const T *)d_ids, n, vs, hi,
+                               c->d_proj_toff, c->d_proj_tab, c->d_dec_off, (unsigned long long)total, (T *)d_out, tile, W);
+        });
+        LAUNCHCHK(c, "k_project_place");
+        return BPE_OK;
+    };
+    return resident_two_pass(c, id_width, n, d_doc_token_offsets, k, d_doc_out_offsets, d_out, out_cap, n_out, bad_index, txt,
+                             len, place);
 }

@@ -39,13 +39,13 @@ extern "C" int bpe_rows_resident(bpe_ctx *c, const int32_t *d_ids, uint64_t n, c
         return fail(c, BPE_E_LIMIT, "document index and position are int32: n + n_docs must stay below 2^31");
     if (n_docs >= (1ull << 48)) return fail(c, BPE_E_LIMIT, "%llu documents exceed 2^48-1", (unsigned long long)n_docs);
     HIPCHK(c, hipSetDevice(c->device));
-    unsigned long long *d_bad = c->d_scratch, *d_ends = c->d_scratch + 1;
-    HIPCHK(c, hipMemsetAsync(d_bad, 0xFF, sizeof(unsigned long long), c->stream));
+    auto *w = &c->d_scratch->rows;
+    HIPCHK(c, hipMemsetAsync(&w->bad, 0xFF, sizeof(unsigned long long), c->stream));
     hipLaunchKernelGGL(k_rows_check, dim3(grid_for(n_docs + 1, 256, c->num_cus * 8)), dim3(256), 0, c->stream,
-                       (const unsigned long long *)d_doc_offsets, n_docs, n, d_bad, d_ends);
+                       (const unsigned long long *)d_doc_offsets, n_docs, n, &w->bad, w->ends);
     LAUNCHCHK(c, "k_rows_check");
     unsigned long long hb[3] = {0, 0, 0};  // {first bad entry, off[0], off[n_docs]}
-    HIPCHK(c, hipMemcpyAsync(hb, c->d_scratch, sizeof hb, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(hb, w, sizeof hb, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     if (hb[0] != ~0ull) {
         if (bad_doc) *bad_doc = hb[0];
@@ -84,20 +84,16 @@ extern "C" int bpe_rows_resident(bpe_ctx *c, const int32_t *d_ids, uint64_t n, c
     if (pack) {
         const bool doc = has_sep || d_doc_index || d_pos;
         const size_t lds = doc ? 2 * sizeof(unsigned long long) + (((size_t)A.stage * sizeof(uint32_t) + 15) & ~(size_t)15) : 0;
-        if (doc && row_width == 4)
-            hipLaunchKernelGGL((k_rows_pack<int32_t, true>), grid, dim3(ROWS_THREADS), lds, c->stream, A);
-        else if (doc)
-            hipLaunchKernelGGL((k_rows_pack<int64_t, true>), grid, dim3(ROWS_THREADS), lds, c->stream, A);
-        else if (row_width == 4)
-            hipLaunchKernelGGL((k_rows_pack<int32_t, false>), grid, dim3(ROWS_THREADS), lds, c->stream, A);
-        else
-            hipLaunchKernelGGL((k_rows_pack<int64_t, false>), grid, dim3(ROWS_THREADS), lds, c->stream, A);
+        by_width(row_width, [&](auto t) {
+            using T = decltype(t);
+            if (doc) hipLaunchKernelGGL((k_rows_pack<T, true>), grid, dim3(ROWS_THREADS), lds, c->stream, A);
+            else hipLaunchKernelGGL((k_rows_pack<T, false>), grid, dim3(ROWS_THREADS), lds, c->stream, A);
+        });
         LAUNCHCHK(c, "k_rows_pack");
     } else {
-        if (row_width == 4)
-            hipLaunchKernelGGL(k_rows_per_doc<int32_t>, grid, dim3(ROWS_THREADS), 0, c->stream, A);
-        else
-            hipLaunchKernelGGL(k_rows_per_doc<int64_t>, grid, dim3(ROWS_THREADS), 0, c->stream, A);
+        by_width(row_width, [&](auto t) {
+            hipLaunchKernelGGL(k_rows_per_doc<decltype(t)>, grid, dim3(ROWS_THREADS), 0, c->stream, A);
+        });
         LAUNCHCHK(c, "k_rows_per_doc");
     }
     HIPCHK(c, hipStreamSynchronize(c->stream));

@@ -14,7 +14,7 @@ static int spans_meta(bpe_ctx *c) {
         c->cap_dec_meta = c->dec_V;
     }
     if (c->dec_V) {
-        unsigned long long *d_limit = c->d_scratch;
+        unsigned long long *d_limit = &c->d_scratch->count;
         HIPCHK(c, hipMemsetAsync(d_limit, 0, sizeof(unsigned long long), c->stream));
         hipLaunchKernelGGL(k_spans_meta, dim3(grid_for(c->dec_V, 4, c->num_cus * 8)), dim3(256), 0, c->stream, c->d_dec_blob,
                            c->d_dec_voff, c->dec_V, c->d_dec_meta, d_limit);
@@ -50,14 +50,8 @@ extern "C" int bpe_token_spans_resident(bpe_ctx *c, const void *d_ids, int32_t i
     c->dec_have_result = false;
     TRY(spans_meta(c));
     const bool docs = d_doc_offsets != nullptr;
-    const uint64_t nb = (n + SCAN_TILE - 1) / SCAN_TILE;
-    if (n > c->cap_dec_n) {  // (as bpe_decode_batch_resident grows it)
-        TRY(dev_realloc(c, c->d_dec_ids, (size_t)n));
-        TRY(dev_realloc(c, c->d_dec_len, (size_t)n));
-        TRY(dev_realloc(c, c->d_dec_off, (size_t)n + 1));
-        TRY(dev_realloc(c, c->d_dec_bsum, (size_t)nb + 1));
-        c->cap_dec_n = n;
-    }
+    const uint64_t nb = scan_tiles(n);
+    TRY(ensure_dec_scratch(c, n));
     if (n > c->cap_spn_n) {
         c->cap_spn_n = 0;
         TRY(dev_realloc(c, c->d_spn_off, (size_t)n + 1));
@@ -70,9 +64,10 @@ extern "C" int bpe_token_spans_resident(bpe_ctx *c, const void *d_ids, int32_t i
         c->cap_spn_docs = n_docs + 1;
     }
     // {first bad position, total bytes, total leads, first bad offset entry, off[0], off[n_docs]}
-    unsigned long long *d_bad = c->d_scratch, *d_totals = c->d_scratch + 1, *d_docbad = c->d_scratch + 3, *d_ends = c->d_scratch + 4;
+    auto *w = &c->d_scratch->spans;
+    unsigned long long *d_bad = &w->bad, *d_totals = w->totals, *d_docbad = &w->docbad, *d_ends = w->ends;
     uint32_t *d_len = c->d_dec_len, *d_lw = (uint32_t *)c->d_dec_ids;
-    HIPCHK(c, hipMemsetAsync(d_bad, 0xFF, 4 * sizeof(unsigned long long), c->stream));
+    HIPCHK(c, hipMemsetAsync(d_bad, 0xFF, 4 * sizeof(unsigned long long), c->stream));  // bad, totals, docbad
     if (docs) {
         hipLaunchKernelGGL(k_rows_check, dim3(grid_for(n_docs + 1, 256, c->num_cus * 8)), dim3(256), 0, c->stream,
                            (const unsigned long long *)d_doc_offsets, n_docs, n, d_docbad, d_ends);
@@ -83,12 +78,11 @@ extern "C" int bpe_token_spans_resident(bpe_ctx *c, const void *d_ids, int32_t i
     } else {
         TRY(prof_begin(c, BPE_PROF_DECODE, (uint64_t)id_width * n));
         const dim3 grid(grid_for(n, 256, c->num_cus * 8));
-        if (id_width == 4)
-            hipLaunchKernelGGL(k_spans_len<int32_t>, grid, dim3(256), 0, c->stream, (const int32_t *)d_ids, n, c->d_dec_voff,
+        by_width(id_width, [&](auto t) {
+            using T = decltype(t);
+            hipLaunchKernelGGL(k_spans_len<T>, grid, dim3(256), 0, c->stream, (const T *)d_ids, n, c->d_dec_voff,
                                c->d_dec_meta, c->dec_V_dense, c->d_dec_sparse, c->dec_n_sparse, d_len, d_lw, d_bad);
-        else
-            hipLaunchKernelGGL(k_spans_len<int64_t>, grid, dim3(256), 0, c->stream, (const int64_t *)d_ids, n, c->d_dec_voff,
-                               c->d_dec_meta, c->dec_V_dense, c->d_dec_sparse, c->dec_n_sparse, d_len, d_lw, d_bad);
+        });
         LAUNCHCHK(c, "k_spans_len");
         hipLaunchKernelGGL(k_spans_blocksum, dim3((unsigned)nb), dim3(256), 0, c->stream, d_len, d_lw, n, c->d_dec_bsum,
                            c->d_spn_bsum);
@@ -99,7 +93,7 @@ extern "C" int bpe_token_spans_resident(bpe_ctx *c, const void *d_ids, int32_t i
         TRY(prof_end(c));
     }
     unsigned long long hb[6] = {0, 0, 0, 0, 0, 0};
-    HIPCHK(c, hipMemcpyAsync(hb, c->d_scratch, sizeof hb, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(hb, w, sizeof hb, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     if (hb[0] != ~0ull || hb[3] != ~0ull) {  // nothing has been written to the span arrays
         if (bad_index) *bad_index = hb[0];

@@ -103,6 +103,66 @@ def _concat_chunks(chunks):
     return b"".join(chunks), offs
 
 
+# ---------------------------------------------------------------------------
+# argument handling shared by the methods over ids that live in HBM
+
+def _cuda_device(device):
+    """torch.device of one GPU from an index, a 'cuda:<index>' or None (the process-wide engine's)"""
+    import torch
+    if device is None:
+        device = _default_device()
+    dev = torch.device("cuda", device) if isinstance(device, int) else torch.device(device)
+    if dev.type != "cuda" or dev.index is None:
+        raise ValueError("device must name one GPU: an index, or 'cuda:<index>'")
+    return dev
+
+
+def _host_array(ids):
+    """a list or an array of integers on the host -> contiguous 1-D int64"""
+    arr = np.asarray(ids)
+    if arr.size and arr.dtype.kind not in "iu":
+        raise TypeError("token ids must be integers")
+    if arr.ndim > 1:
+        raise TypeError("token ids must be a flat list or a 1-D array")
+    return np.ascontiguousarray(arr.astype(np.int64, copy=False).reshape(-1))
+
+
+def _check_ids(ids, dtypes, cuda=True):
+    """TypeError unless `ids` is a 1-D contiguous torch tensor of one of `dtypes` on the GPU.  cuda=False leaves the last
+    part out, for a method that owes its caller other errors first; it then calls again with everything."""
+    import torch
+    if not isinstance(ids, torch.Tensor) or (cuda and not ids.is_cuda) or ids.dim() != 1 or not ids.is_contiguous() \
+            or ids.dtype not in dtypes:
+        names = " or ".join(str(d).split(".")[-1] for d in dtypes)
+        raise TypeError(f"ids must be a 1-D contiguous {names} torch tensor on the GPU")
+
+
+def _check_doc_offsets(doc_offsets, dev, strict):
+    """doc_offsets as _place_doc_offsets takes it.  A tensor must hold integers on `dev`.  strict: anything else must
+    hold integers too (it comes back as an array), and there must be the n_docs + 1 >= 1 entries of a document list."""
+    import torch
+    if isinstance(doc_offsets, torch.Tensor):
+        if doc_offsets.device != dev or doc_offsets.dtype not in (torch.int32, torch.int64):
+            raise TypeError("doc_offsets must be an integer tensor on the device of ids")
+        count = doc_offsets.numel()
+    elif strict:
+        doc_offsets = np.asarray(doc_offsets)
+        if doc_offsets.size and doc_offsets.dtype.kind not in "iu":
+            raise TypeError("doc_offsets must be integers")
+        count = doc_offsets.size
+    if strict and count < 1:
+        raise ValueError("doc_offsets needs n_docs + 1 entries")
+    return doc_offsets
+
+
+def _place_doc_offsets(doc_offsets, dev):
+    """checked doc_offsets -> flat contiguous int64 tensor on `dev`"""
+    import torch
+    if isinstance(doc_offsets, torch.Tensor):
+        return doc_offsets.to(torch.int64).contiguous().reshape(-1)
+    return torch.from_numpy(np.ascontiguousarray(doc_offsets, dtype=np.int64).reshape(-1)).to(dev)
+
+
 class Tokenizer:
     """Base class: state, vocab construction, save/load (base.py:66-165)."""
 
@@ -234,15 +294,53 @@ class Tokenizer:
                 if j is None:
                     raise self._invalid_token(int(arr[p]))
                 arr[p] = j
-        eng = engine()
-        # the table stays resident per engine: _decode_owner = (the blob uploaded, its sparse list is uploaded too)
-        if getattr(eng, "_decode_owner", (None, False))[0] is not blob:
-            eng.decode_set_vocab(blob, offs)
-            eng._decode_owner = (blob, False)
-        res = eng.decode_batch(arr.astype(np.int32), doc_offsets)
+        res = self._decode_engine(None, sparse=False).decode_batch(arr.astype(np.int32), doc_offsets)
         if doc_offsets is None:
             return self._finish_bytes(res)
         return self._finish_bytes(res[0]), res[1]
+
+    def _decode_engine(self, device, sparse=True):
+        """The engine of `device` with this tokenizer's decode table resident.  sparse: the table as the resident calls
+        read it (_decode_table_resident) together with its sparse id list; without, the table of decode_batch, which
+        resolves those ids on the host.  The table stays resident per engine: _decode_owner = (the blob uploaded, its
+        sparse list is uploaded too)."""
+        if sparse:
+            blob, offs, V, sparse_ids = self._decode_table_resident()
+        else:
+            blob, offs = self._decode_table()[:2]
+        eng = engine(device)
+        owner = getattr(eng, "_decode_owner", (None, False))
+        if owner[0] is not blob or (sparse and not owner[1]):
+            eng.decode_set_vocab(blob, offs)
+            if sparse:
+                eng.decode_set_sparse(sparse_ids, V)
+            eng._decode_owner = (blob, sparse)
+        return eng
+
+    def _resident_fill(self, ids, out, out_dtype, docs, unit, verb, native_call, count_only=False):
+        """The count-then-fill protocol of decode_batch_resident and _project: out[:total], filled by
+        native_call(dst pointer, dst capacity, offsets pointer, k, output offsets pointer) -> total.  out=None: sized by a
+        count-only call first.  docs: (token offsets, room for the output offsets) on the device, or None.  The
+        library's InvalidToken and OutputTooSmall become the caller's errors ("... <unit>, the batch <verb> to ...")."""
+        import torch
+
+        def call(dst, with_docs):
+            room = (0, 0) if dst is None else (dst.data_ptr(), dst.numel())
+            where = (docs[0].data_ptr(), docs[0].numel(), docs[1].data_ptr()) if with_docs else (0, 0, 0)
+            try:
+                return native_call(*room, *where)
+            except _native.InvalidToken as e:
+                raise self._invalid_token(int(ids[e.args[0]].item())) from None
+            except _native.OutputTooSmall as e:
+                raise ValueError(f"out holds {dst.numel()} {unit}, the batch {verb} to {e.needed}") from None
+
+        if count_only:
+            return call(None, False)
+        if out is None:
+            out = torch.empty(call(None, False), dtype=out_dtype, device=ids.device)
+        elif out.numel() == 0 and call(None, False):  # (no room at all is a count-only call to the library)
+            raise ValueError(f"out holds 0 {unit}")
+        return out[:call(out, docs is not None and docs[0].numel() > 0)]
 
     def _resident_blob(self, blob):
         """the table bytes as the device-resident decode emits them (_finish_bytes applied to the table)"""
@@ -270,50 +368,22 @@ class Tokenizer:
         into (the view out[:total] is returned; ValueError if it is too small); without it the batch is measured by
         a count-only call first.  Unknown ids raise what decode() raises, for the first such id."""
         import torch
-        if not isinstance(ids, torch.Tensor) or not ids.is_cuda or ids.dim() != 1 or not ids.is_contiguous() \
-                or ids.dtype not in (torch.int32, torch.int64):
-            raise TypeError("ids must be a 1-D contiguous int32 or int64 torch tensor on the GPU")
+        _check_ids(ids, (torch.int32, torch.int64))
         dev = ids.device
         if out is not None and (not isinstance(out, torch.Tensor) or out.device != dev or out.dtype != torch.uint8
                                 or out.dim() != 1 or not out.is_contiguous()):
             raise TypeError("out must be a 1-D contiguous uint8 torch tensor on the device of ids")
-        blob, offs, V, sparse_ids = self._decode_table_resident()
-        eng = engine(dev.index)
-        owner = getattr(eng, "_decode_owner", (None, False))
-        if owner[0] is not blob or not owner[1]:
-            eng.decode_set_vocab(blob, offs)
-            eng.decode_set_sparse(sparse_ids, V)
-            eng._decode_owner = (blob, True)
-        n, width = ids.numel(), ids.element_size()
-        doff, boff, k = None, None, 0
+        eng = self._decode_engine(dev.index)
+        docs = None
         if doc_offsets is not None:
-            if isinstance(doc_offsets, torch.Tensor):
-                if doc_offsets.device != dev or doc_offsets.dtype not in (torch.int32, torch.int64):
-                    raise TypeError("doc_offsets must be an integer tensor on the device of ids")
-                doff = doc_offsets.to(torch.int64).contiguous().reshape(-1)
-            else:
-                doff = torch.from_numpy(np.ascontiguousarray(doc_offsets, dtype=np.int64).reshape(-1)).to(dev)
-            k = doff.numel()
-            boff = torch.empty(k, dtype=torch.int64, device=dev)
+            doff = _place_doc_offsets(_check_doc_offsets(doc_offsets, dev, strict=False), dev)
+            docs = (doff, torch.empty(doff.numel(), dtype=torch.int64, device=dev))
         torch.cuda.current_stream(dev).synchronize()  # the caller's pending writes to ids (and uploads above) are done
-
-        def call(dst, with_docs):
-            try:
-                return eng.decode_batch_resident(ids.data_ptr(), width, n, doff.data_ptr() if with_docs else 0,
-                                                 k if with_docs else 0, 0 if dst is None else dst.data_ptr(),
-                                                 0 if dst is None else dst.numel(), boff.data_ptr() if with_docs else 0)
-            except _native.InvalidToken as e:
-                raise self._invalid_token(int(ids[e.args[0]].item())) from None
-            except _native.OutputTooSmall as e:
-                raise ValueError(f"out holds {dst.numel()} bytes, the batch decodes to {e.needed}") from None
-
-        if out is None:
-            out = torch.empty(call(None, False), dtype=torch.uint8, device=dev)
-        elif out.numel() == 0 and call(None, False):  # (no room at all is a count-only call to the library)
-            raise ValueError("out holds 0 bytes")
-        total = call(out, k > 0)
-        res = out[:total]
-        return res if doc_offsets is None else (res, boff)
+        res = self._resident_fill(
+            ids, out, torch.uint8, docs, "bytes", "decodes",
+            lambda dst, cap, d_off, k, d_boff: eng.decode_batch_resident(ids.data_ptr(), ids.element_size(), ids.numel(),
+                                                                         d_off, k, dst, cap, d_boff))
+        return res if doc_offsets is None else (res, docs[1])
 
     # -- the offset mapping of ids that live in HBM (DESIGN 4.5) -----------------------
     _SPAN_UNITS = ("char", "byte", "both")
@@ -334,36 +404,14 @@ class Tokenizer:
         import torch
         if unit not in self._SPAN_UNITS:
             raise ValueError(f"unit={unit!r} not understood: 'char', 'byte' or 'both'")
-        if not isinstance(ids, torch.Tensor) or ids.dim() != 1 or not ids.is_contiguous() \
-                or ids.dtype not in (torch.int32, torch.int64):
-            raise TypeError("ids must be a 1-D contiguous int32 or int64 torch tensor on the GPU")
+        _check_ids(ids, (torch.int32, torch.int64), cuda=False)
         dev = ids.device
         if doc_offsets is not None:
-            if isinstance(doc_offsets, torch.Tensor):
-                if doc_offsets.device != dev or doc_offsets.dtype not in (torch.int32, torch.int64):
-                    raise TypeError("doc_offsets must be an integer tensor on the device of ids")
-            else:
-                doc_offsets = np.asarray(doc_offsets)
-                if doc_offsets.size and doc_offsets.dtype.kind not in "iu":
-                    raise TypeError("doc_offsets must be integers")
-            if (doc_offsets.numel() if isinstance(doc_offsets, torch.Tensor) else doc_offsets.size) < 1:
-                raise ValueError("doc_offsets needs n_docs + 1 entries")
-        if not ids.is_cuda:
-            raise TypeError("ids must be a 1-D contiguous int32 or int64 torch tensor on the GPU")
-        blob, offs, V, sparse_ids = self._decode_table_resident()
-        eng = engine(dev.index)
-        owner = getattr(eng, "_decode_owner", (None, False))
-        if owner[0] is not blob or not owner[1]:
-            eng.decode_set_vocab(blob, offs)
-            eng.decode_set_sparse(sparse_ids, V)
-            eng._decode_owner = (blob, True)
+            doc_offsets = _check_doc_offsets(doc_offsets, dev, strict=True)
+        _check_ids(ids, (torch.int32, torch.int64))  # (a bad doc_offsets is reported even for ids on the host)
+        eng = self._decode_engine(dev.index)
         n, width = ids.numel(), ids.element_size()
-        doff = None
-        if doc_offsets is not None:
-            if isinstance(doc_offsets, torch.Tensor):
-                doff = doc_offsets.to(torch.int64).contiguous().reshape(-1)
-            else:
-                doff = torch.from_numpy(np.ascontiguousarray(doc_offsets, dtype=np.int64).reshape(-1)).to(dev)
+        doff = None if doc_offsets is None else _place_doc_offsets(doc_offsets, dev)
         bspans = torch.empty((n, 2), dtype=torch.int64, device=dev) if unit != "char" else None
         cspans = torch.empty((n, 2), dtype=torch.int64, device=dev) if unit != "byte" else None
         torch.cuda.current_stream(dev).synchronize()  # the caller's pending writes to ids (and the upload above) are done
@@ -380,23 +428,13 @@ class Tokenizer:
         them for unit="both").  device: the GPU's index (default: the process-wide engine's)."""
         if unit not in self._SPAN_UNITS:
             raise ValueError(f"unit={unit!r} not understood: 'char', 'byte' or 'both'")
-        arr = np.asarray(ids)
-        if arr.size and arr.dtype.kind not in "iu":
-            raise TypeError("token ids must be integers")
-        if arr.ndim > 1:
-            raise TypeError("token ids must be a flat list or a 1-D array")
-        arr = np.ascontiguousarray(arr.astype(np.int64, copy=False).reshape(-1))
+        arr = _host_array(ids)
         if doc_offsets is not None:
             doc_offsets = np.asarray(doc_offsets)
             if doc_offsets.size and doc_offsets.dtype.kind not in "iu":
                 raise TypeError("doc_offsets must be integers")
         import torch
-        if device is None:
-            device = _default_device()
-        dev = torch.device("cuda", device) if isinstance(device, int) else torch.device(device)
-        if dev.type != "cuda" or dev.index is None:
-            raise ValueError("device must name one GPU: an index, or 'cuda:<index>'")
-        res = self.token_spans_resident(torch.from_numpy(arr).to(dev), doc_offsets, unit=unit)
+        res = self.token_spans_resident(torch.from_numpy(arr).to(_cuda_device(device)), doc_offsets, unit=unit)
         return tuple(t.cpu().numpy() for t in res) if unit == "both" else res.cpu().numpy()
 
     def _with_offsets(self, encode, text, unit):
@@ -486,61 +524,35 @@ class Tokenizer:
 
     @staticmethod
     def _host_ids(ids):
-        arr = np.asarray(ids)
-        if arr.size and arr.dtype.kind not in "iu":
-            raise TypeError("token ids must be integers")
-        if arr.ndim > 1:
-            raise TypeError("token ids must be a flat list or a 1-D array")
+        arr = _host_array(ids)
         import torch
-        arr = np.ascontiguousarray(arr.astype(np.int64, copy=False).reshape(-1))
-        return torch.from_numpy(arr).to(torch.device("cuda", _default_device()))
+        return torch.from_numpy(arr).to(_cuda_device(None))
 
     def _project(self, ids, vocab_size, doc_offsets, out, count_only):
         import torch
-        if not isinstance(ids, torch.Tensor) or not ids.is_cuda or ids.dim() != 1 or not ids.is_contiguous() \
-                or ids.dtype not in (torch.int32, torch.int64):
-            raise TypeError("ids must be a 1-D contiguous int32 or int64 torch tensor on the GPU")
+        _check_ids(ids, (torch.int32, torch.int64))
         dev = ids.device
         if out is not None and (not isinstance(out, torch.Tensor) or out.device != dev or out.dtype != ids.dtype
                                 or out.dim() != 1 or not out.is_contiguous()):
             raise TypeError("out must be a 1-D contiguous torch tensor of the dtype and on the device of ids")
-        if doc_offsets is not None and isinstance(doc_offsets, torch.Tensor) \
-                and (doc_offsets.device != dev or doc_offsets.dtype not in (torch.int32, torch.int64)):
-            raise TypeError("doc_offsets must be an integer tensor on the device of ids")
+        if doc_offsets is not None:
+            _check_doc_offsets(doc_offsets, dev, strict=False)
         pairs, pass_ids = self._project_args(vocab_size)
         eng = engine(dev.index)
         if getattr(eng, "_project_owner", None) is not pairs:  # (a new array whenever merges or special tokens changed)
             eng.project_set_merges(pairs, pass_ids)
             eng._project_owner = pairs
-        n, width = ids.numel(), ids.element_size()
-        doff, ooff, k = None, None, 0
+        docs = None
         if doc_offsets is not None:
-            if isinstance(doc_offsets, torch.Tensor):
-                doff = doc_offsets.to(torch.int64).contiguous().reshape(-1)
-            else:
-                doff = torch.from_numpy(np.ascontiguousarray(doc_offsets, dtype=np.int64).reshape(-1)).to(dev)
-            k = doff.numel()
-            ooff = torch.empty(k, dtype=torch.int64, device=dev)
+            doff = _place_doc_offsets(doc_offsets, dev)
+            docs = (doff, torch.empty(doff.numel(), dtype=torch.int64, device=dev))
         torch.cuda.current_stream(dev).synchronize()  # the caller's pending writes to ids (and uploads above) are done
-
-        def call(dst, with_docs):
-            try:
-                return eng.project_resident(ids.data_ptr(), width, n, int(vocab_size), doff.data_ptr() if with_docs else 0,
-                                            k if with_docs else 0, 0 if dst is None else dst.data_ptr(),
-                                            0 if dst is None else dst.numel(), ooff.data_ptr() if with_docs else 0)
-            except _native.InvalidToken as e:
-                raise self._invalid_token(int(ids[e.args[0]].item())) from None
-            except _native.OutputTooSmall as e:
-                raise ValueError(f"out holds {dst.numel()} ids, the batch projects to {e.needed}") from None
-
-        if count_only:
-            return call(None, False)
-        if out is None:
-            out = torch.empty(call(None, False), dtype=ids.dtype, device=dev)
-        elif out.numel() == 0 and call(None, False):  # (no room at all is a count-only call to the library)
-            raise ValueError("out holds 0 ids")
-        total = call(out, k > 0)
-        return out[:total], ooff
+        res = self._resident_fill(
+            ids, out, ids.dtype, docs, "ids", "projects",
+            lambda dst, cap, d_off, k, d_ooff: eng.project_resident(ids.data_ptr(), ids.element_size(), ids.numel(),
+                                                                    int(vocab_size), d_off, k, dst, cap, d_ooff),
+            count_only)
+        return res if count_only else (res, None if docs is None else docs[1])
 
     # -- fixed-length rows from ids that live in HBM ---------------------
     def rows_resident(self, ids, doc_offsets, row_len, *, stride=None, sep=None, pad=0, mode="pack", truncate="right",
@@ -595,31 +607,16 @@ class Tokenizer:
         if dtype not in (torch.int32, torch.int64):
             raise ValueError("dtype must be torch.int32 or torch.int64")
         # -- tensors
-        if not isinstance(ids, torch.Tensor) or ids.dim() != 1 or ids.dtype != torch.int32 or not ids.is_contiguous():
-            raise TypeError("ids must be a 1-D contiguous int32 torch tensor on the GPU")
+        _check_ids(ids, (torch.int32,), cuda=False)
         dev = ids.device
-        if isinstance(doc_offsets, torch.Tensor):
-            if doc_offsets.device != dev or doc_offsets.dtype not in (torch.int32, torch.int64):
-                raise TypeError("doc_offsets must be an integer tensor on the device of ids")
-            n_off = doc_offsets.numel()
-        else:
-            doc_offsets = np.asarray(doc_offsets)
-            if doc_offsets.size and doc_offsets.dtype.kind not in "iu":
-                raise TypeError("doc_offsets must be integers")
-            n_off = doc_offsets.size
-        if n_off < 1:
-            raise ValueError("doc_offsets needs n_docs + 1 entries")
+        doc_offsets = _check_doc_offsets(doc_offsets, dev, strict=True)
         if out is not None:
             if not isinstance(out, torch.Tensor) or out.device != dev or out.dtype != dtype or not out.is_contiguous():
                 raise TypeError("out must be a contiguous tensor of `dtype` on the device of ids")
-        if not ids.is_cuda:
-            raise TypeError("ids must be a 1-D contiguous int32 torch tensor on the GPU")
+        _check_ids(ids, (torch.int32,))
         # -- the device
-        n, n_docs = ids.numel(), n_off - 1
-        if isinstance(doc_offsets, torch.Tensor):
-            doff = doc_offsets.to(torch.int64).contiguous().reshape(-1)
-        else:
-            doff = torch.from_numpy(np.ascontiguousarray(doc_offsets, dtype=np.int64).reshape(-1)).to(dev)
+        doff = _place_doc_offsets(doc_offsets, dev)
+        n, n_docs = ids.numel(), doff.numel() - 1
         flags = (_native.ROWS_HAS_SEP if sep is not None else 0) | (_native.ROWS_TRUNC_LEFT if truncate == "left" else 0) \
             | (_native.ROWS_PAD_LEFT if pad_side == "left" else 0)
         width = 4 if dtype == torch.int32 else 8
@@ -827,6 +824,13 @@ class RegexTokenizer(Tokenizer):
         enc = [t.encode("utf-8") for t in texts]
         if not enc:
             return np.empty(0, np.int32), np.zeros(1, np.uint64)
+        data, offs, first = self._split_texts(texts, enc)
+        ids, out_off = self._encode_flat(data, offs)
+        return ids, out_off[first]
+
+    def _split_texts(self, texts, enc):
+        """Every text (enc: their UTF-8 bytes, at least one) split on its own: (the chunks' bytes back to back, chunk
+        start offsets, int64 index of every text's first chunk and, last, the number of chunks)."""
         which = _NATIVE_SPLIT.get(self.compiled_pattern.pattern)
         if which is not None:
             data = b"".join(enc)
@@ -839,9 +843,7 @@ class RegexTokenizer(Tokenizer):
                 pieces += [p for p in self._split(t) if p]
                 first.append(len(pieces))
             data, offs = _concat_chunks(pieces)
-            first = np.array(first, dtype=np.uint64)
-        ids, out_off = self._encode_flat(data, offs)
-        return ids, out_off[first.astype(np.int64)]
+        return data, offs, np.ascontiguousarray(first, dtype=np.int64)
 
     def encode_ordinary_batch_resident(self, texts, device=None):
         """encode_ordinary_batch() with the ids left in HBM: returns (ids, doc_offsets), an int32 torch tensor on the
@@ -849,27 +851,11 @@ class RegexTokenizer(Tokenizer):
         offsets on the same GPU.  The host splits the texts and uploads their bytes once; ids and offsets never come
         back.  device: the GPU's index (default: the process-wide engine's)."""
         import torch
-        if device is None:
-            device = _default_device()
-        dev = torch.device("cuda", device) if isinstance(device, int) else torch.device(device)
-        if dev.type != "cuda" or dev.index is None:
-            raise ValueError("device must name one GPU: an index, or 'cuda:<index>'")
+        dev = _cuda_device(device)
         enc = [t.encode("utf-8") for t in texts]
         if not any(enc):  # nothing to encode: no engine call
             return torch.empty(0, dtype=torch.int32, device=dev), torch.zeros(len(enc) + 1, dtype=torch.int64, device=dev)
-        which = _NATIVE_SPLIT.get(self.compiled_pattern.pattern)
-        if which is not None:
-            data = b"".join(enc)
-            doff = np.zeros(len(enc), dtype=np.uint64)
-            np.cumsum(np.fromiter((len(e) for e in enc[:-1]), dtype=np.uint64, count=len(enc) - 1), out=doff[1:])
-            offs, first = _native.split_docs(data, doff, which)
-        else:  # any other pattern: the regex module, one text at a time
-            pieces, first = [], [0]
-            for t in texts:
-                pieces += [p for p in self._split(t) if p]
-                first.append(len(pieces))
-            data, offs = _concat_chunks(pieces)
-        first = np.ascontiguousarray(first, dtype=np.int64)[:len(enc) + 1]
+        data, offs, first = self._split_texts(texts, enc)
         pairs, mids = self._merge_table()
         data = self._prepare_chunk(data)
         d_bytes = torch.from_numpy(np.frombuffer(bytearray(data), dtype=np.uint8)).to(dev)
