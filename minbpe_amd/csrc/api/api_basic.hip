@@ -2,6 +2,15 @@
 // Part of bpe_api.hip, which includes the parts in order (one translation unit).
 
 // ============================================================================
+namespace {
+// the end of a ctx, whole or half made: its memory and events (the members free themselves), then its stream
+void ctx_free(bpe_ctx *c) {
+    hipStream_t stream = c->own_stream ? c->stream : nullptr;
+    delete c;
+    if (stream) (void)hipStreamDestroy(stream);
+}
+}  // namespace
+
 extern "C" {
 
 const char *bpe_version(void) { return "minbpe_amd libbpe_hip 0.1 (gfx950)"; }
@@ -22,7 +31,7 @@ int bpe_create(int device_id, bpe_ctx **out) {
     c->device = device_id;
     auto bail = [&](const char *what, hipError_t er) {
         int rc = fail(nullptr, BPE_E_HIP, "%s failed: %s", what, hipGetErrorString(er));
-        delete c;
+        ctx_free(c);
         return rc;
     };
     if ((e = hipSetDevice(device_id)) != hipSuccess) return bail("hipSetDevice", e);
@@ -44,9 +53,11 @@ int bpe_create(int device_id, bpe_ctx **out) {
     if ((e = hipFuncSetAttribute((const void *)bpe::bpe_g4::k_index_build, hipFuncAttributeMaxDynamicSharedMemorySize,
                                  bpe::bpe_g4::IDX_H * 4)) != hipSuccess)
         return bail("hipFuncSetAttribute(dynamic LDS)", e);
-    if ((e = hipMalloc((void **)&c->d_st, sizeof(DevState))) != hipSuccess) return bail("hipMalloc", e);
-    if ((e = hipMalloc((void **)&c->d_scratch, SCRATCH_WORDS * sizeof(unsigned long long))) != hipSuccess)
-        return bail("hipMalloc", e);
+    if (dev_once(c, c->d_st, 1) != BPE_OK || dev_once(c, c->d_scratch, 1) != BPE_OK) {
+        g_create_err = c->err;
+        ctx_free(c);
+        return BPE_E_HIP;
+    }
     *out = c;
     return BPE_OK;
 }
@@ -56,31 +67,7 @@ void bpe_destroy(bpe_ctx *c) {
     (void)hipSetDevice(c->device);
     if (c->stream) (void)hipStreamSynchronize(c->stream);
     if (c->comm) (void)bpe_comm_destroy(c);
-    for (ProfEv &ev : c->prof_open) {
-        (void)hipEventDestroy(ev.e0);
-        (void)hipEventDestroy(ev.e1);
-    }
-    for (hipEvent_t ev : c->ev_pool) (void)hipEventDestroy(ev);
-    void *ptrs[] = {c->d_bytes, c->d_offsets, c->d_ids[0], c->d_ids[1], c->d_mat,  c->d_first,
-                    c->d_rowmax, c->d_st,     c->d_tsum,   c->d_tile_off, c->d_tile_sin, c->d_sup, c->d_scratch,
-                    c->d_delta,  c->d_dirty_list, c->d_dirty_n, c->d_desc, c->d_gdesc, c->d_enc_tmp, c->d_enc_len, c->d_enc_out,
-                    c->d_enc_off, c->d_enc_bsum, c->d_enc_long, c->d_ht_keys, c->d_ht_vals, c->d_merge_ids,
-                    c->d_dp_folded, c->d_dp_table, c->d_dp_key, c->d_meta[0], c->d_meta[1], c->d_slot_lens,
-                    c->d_slot_off, c->d_slot_bsum, c->d_ids2, c->d_hdr[0], c->d_hdr[1],
-                    c->d_dec_blob, c->d_dec_out, c->d_dec_voff, c->d_dec_off, c->d_dec_bsum, c->d_dec_ids,
-                    c->d_dec_len, c->d_dec_sparse, c->d_dec_meta, c->d_spn_off, c->d_spn_bsum, c->d_spn_base, c->d_wexp, c->d_round_lb, c->d_dp_ckey, c->d_dp_cfold, c->d_hdr2[0], c->d_hdr2[1], c->d_stage, c->d_idx, c->d_idx_tmp, c->d_idx_dirty, c->d_removed, c->d_smask, c->d_cand, c->d_dbits, c->d_lean_res, c->d_lean_sum, c->d_enc_tab, c->d_enc_rep, c->d_enc_mid, c->d_enc_midn, c->d_chain_req, c->d_pool, c->d_pool_gather, c->d_enc_huge};
-    for (void *p : ptrs)
-        if (p) (void)hipFree(p);
-    if (c->h_rec) (void)hipHostFree(c->h_rec);
-    if (c->h_srec) (void)hipHostFree(c->h_srec);
-    if (c->h_stage) (void)hipHostFree(c->h_stage);
-    for (hipEvent_t ev : c->ev_stage)
-        if (ev) (void)hipEventDestroy(ev);
-    for (void *p : {(void *)c->d_step_pub, (void *)c->d_step_bar, (void *)c->d_step_stamps, (void *)c->d_forced,
-                    (void *)c->d_proj_pass, (void *)c->d_proj_tab, (void *)c->d_proj_toff})
-        if (p) (void)hipFree(p);
-    if (c->own_stream && c->stream) (void)hipStreamDestroy(c->stream);
-    delete c;
+    ctx_free(c);
 }
 
 int bpe_set_stream(bpe_ctx *c, void *hip_stream) {
@@ -90,165 +77,6 @@ int bpe_set_stream(bpe_ctx *c, void *hip_stream) {
     if (c->own_stream) HIPCHK(c, hipStreamDestroy(c->stream));
     c->stream = (hipStream_t)hip_stream;
     c->own_stream = false;
-    return BPE_OK;
-}
-
-int bpe_set_option(bpe_ctx *c, const char *name, int64_t value) {
-    if (!c || !name) return BPE_E_ARG;
-    if (!strcmp(name, "mode")) {
-        if (value != 0 && value != 1) return fail(c, BPE_E_ARG, "mode must be 0 or 1");
-        c->mode = (int)value;
-    } else if (!strcmp(name, "profile")) {
-        if (value < 0 || value > 2) return fail(c, BPE_E_ARG, "profile must be 0, 1 or 2");
-        c->profile = (int)value;
-    } else if (!strcmp(name, "k1")) {
-        c->k1 = (int)value;
-    } else if (!strcmp(name, "scan_sup")) {
-        if (value < 0 || value > (1 << 30)) return fail(c, BPE_E_ARG, "scan_sup: 0 .. 2^30 tiles");
-        c->scan_sup_min = (int)value;
-    } else if (!strcmp(name, "merge")) {
-        if (value != 0 && value != 1) return fail(c, BPE_E_ARG, "merge must be 0 or 1");
-        c->merge_impl = (int)value;
-    } else if (!strcmp(name, "lb_tune")) {
-        c->lb_tune = (uint32_t)value;
-    } else if (!strcmp(name, "fused_rows")) {
-        c->fused_rows = value != 0;
-    } else if (!strcmp(name, "slots")) {
-        if (value < 0 || value > 2) return fail(c, BPE_E_ARG, "slots must be 0, 1 or 2");
-        c->use_slots = (int)value;
-    } else if (!strcmp(name, "sparse")) {
-        if (value < 0 || value > 2) return fail(c, BPE_E_ARG, "sparse must be 0 (never), 1 (auto) or 2 (always)");
-        c->use_sparse = (int)value;
-    } else if (!strcmp(name, "rep_max")) {
-        if (value < 0 || value > 8) return fail(c, BPE_E_ARG, "rep_max must be 0..8");
-        c->rep_max = (int)value;
-    } else if (!strcmp(name, "rep_min")) {
-        if (value < 0 || value > 8) return fail(c, BPE_E_ARG, "rep_min: 0..8");
-        c->rep_min = value;
-    } else if (!strcmp(name, "lds_delta")) {
-        c->lds_delta = value != 0;
-    } else if (!strcmp(name, "exp_no_delta")) {
-        c->exp_no_delta = value != 0;
-    } else if (!strcmp(name, "tie_window")) {
-        c->tie_window = value != 0;
-    } else if (!strcmp(name, "tie_index")) {
-        c->tie_index = value != 0;
-    } else if (!strcmp(name, "sparse_ratio")) {
-        if (value < 1 || value > 64) return fail(c, BPE_E_ARG, "sparse_ratio must be 1..64");
-        c->sparse_ratio = (int)value;
-    } else if (!strcmp(name, "lean")) {
-        if (value < 0 || value > 2) return fail(c, BPE_E_ARG, "lean must be 0 (never), 1 (auto) or 2 (always)");
-        c->lean = (int)value;
-    } else if (!strcmp(name, "lean_backoff")) {
-        c->lean_backoff = value != 0;
-    } else if (!strcmp(name, "lean_count")) {
-        if (value < 0) return fail(c, BPE_E_ARG, "lean_count must be >= 0");
-        c->lean_count = value;
-    } else if (!strcmp(name, "lean_grid")) {
-        if (value < 1 || value > 65535) return fail(c, BPE_E_ARG, "lean_grid must be 1..65535");
-        c->lean_grid = (int)value;
-    } else if (!strcmp(name, "enc_chain")) {
-        c->enc_chain = value != 0;
-    } else if (!strcmp(name, "enc_cache")) {
-        c->enc_cache = value != 0;
-    } else if (!strcmp(name, "enc_hash_bits")) {
-        if (value < 0 || value > 40) return fail(c, BPE_E_ARG, "enc_hash_bits must be 0..40");
-        c->enc_hash_bits = (int)value;
-    } else if (!strcmp(name, "dec_copy")) {
-        c->dec_copy = value != 0;
-    } else if (!strcmp(name, "dec_window")) {
-        if (value < 1024 || value > 32768 || value % 16) return fail(c, BPE_E_ARG, "dec_window: 1024..32768 bytes, a multiple of 16");
-        c->dec_window = (int)value;
-    } else if (!strcmp(name, "dec_tile")) {
-        if (value < 256 || value > 16384 || value % 256) return fail(c, BPE_E_ARG, "dec_tile: 256..16384 tokens, a multiple of 256");
-        c->dec_tile = (int)value;
-    } else if (!strcmp(name, "rows_tile")) {
-        if (value < 64 || value > ROWS_TILE_MAX || value % ROWS_V)
-            return fail(c, BPE_E_ARG, "rows_tile: 64..%u elements, a multiple of %u", ROWS_TILE_MAX, ROWS_V);
-        c->rows_tile = (int)value;
-    } else if (!strcmp(name, "rows_stage")) {
-        if (value < 0 || value > ROWS_STAGE_MAX) return fail(c, BPE_E_ARG, "rows_stage: 0..%u document starts", ROWS_STAGE_MAX);
-        c->rows_stage = (int)value;
-    } else if (!strcmp(name, "spans_stage")) {
-        if (value < 0 || value > SPANS_STAGE_MAX) return fail(c, BPE_E_ARG, "spans_stage: 0..%u document starts", SPANS_STAGE_MAX);
-        c->spans_stage = (int)value;
-    } else if (!strcmp(name, "proj_tile")) {
-        if (value < 64 || value > 16384 || value % 64) return fail(c, BPE_E_ARG, "proj_tile: 64..16384 tokens, a multiple of 64");
-        c->proj_tile = (int)value;
-    } else if (!strcmp(name, "proj_window")) {
-        if (value < 64 || value > PROJ_WINDOW_MAX || value % 4)
-            return fail(c, BPE_E_ARG, "proj_window: 64..%u ids, a multiple of 4", PROJ_WINDOW_MAX);
-        c->proj_window = (int)value;
-    } else if (!strcmp(name, "prof_stride")) {
-        if (value < 1 || value > 1024) return fail(c, BPE_E_ARG, "prof_stride must be 1..1024");
-        c->prof_stride = (int)value;
-    } else if (!strcmp(name, "lean_select")) {
-        c->lean_select = value != 0;
-    } else if (!strcmp(name, "aa_sparse")) {
-        c->aa_sparse = value != 0;
-    } else if (!strcmp(name, "dp_force_comm")) {
-        c->dp_force_comm = value != 0;
-    } else if (!strcmp(name, "dp_kcap")) {
-        if (value < 1 || value > DP_KCAP_MAX) return fail(c, BPE_E_ARG, "dp_kcap must be 1..%d", DP_KCAP_MAX);
-        c->dp_kcap = (int)value;
-    } else if (!strcmp(name, "fuse_load")) {
-        c->fuse_load = value != 0;
-    } else if (!strcmp(name, "chain_dense")) {
-        c->chain_dense = value != 0;
-    } else if (!strcmp(name, "chain_prefetch")) {
-        c->chain_prefetch = value != 0;
-    } else if (!strcmp(name, "count_is_removed")) {
-        c->count_is_removed = value != 0;
-    } else if (!strcmp(name, "enc_long")) {
-        c->enc_long = value != 0;
-    } else if (!strcmp(name, "small_slots")) {
-        if (value < 0 || value > 2) return fail(c, BPE_E_ARG, "small_slots: 0, 1 or 2");
-        c->small_slots = (int)value;
-    } else if (!strcmp(name, "chain_kcap")) {
-        if (value < 1 || value > CH_KSWEEP) return fail(c, BPE_E_ARG, "chain_kcap must be 1..%d", CH_KSWEEP);
-        c->chain_kcap = (int)value;
-    } else if (!strcmp(name, "enc_replay")) {
-        if (value < 0 || value > 1) return fail(c, BPE_E_ARG, "enc_replay must be 0 or 1");
-        c->enc_replay = (int)value;
-    } else if (!strcmp(name, "pinned_upload")) {
-        if (value < 0 || value > 1) return fail(c, BPE_E_ARG, "pinned_upload must be 0 or 1");
-        c->pinned_upload = (int)value;
-    } else if (!strcmp(name, "fuse_step")) {
-        if (value < 0 || value > 1) return fail(c, BPE_E_ARG, "fuse_step must be 0 or 1");
-        c->fuse_step = (int)value;
-    } else if (!strcmp(name, "chain_aa")) {
-        if (value < 0 || value > 1) return fail(c, BPE_E_ARG, "chain_aa must be 0 or 1");
-        c->chain_aa = (int)value;
-    } else if (!strcmp(name, "chain_share_first")) {
-        if (value < 0 || value > 1) return fail(c, BPE_E_ARG, "chain_share_first must be 0 or 1");
-        c->chain_share_first = (int)value;
-    } else if (!strcmp(name, "chain_hash_kmin")) {
-        if (value < 0 || value > 32) return fail(c, BPE_E_ARG, "chain_hash_kmin must be 0..32");
-        c->chain_hash_kmin = (int)value;
-    } else if (!strcmp(name, "pool_hint")) {
-        if (value < 0 || value > 128) return fail(c, BPE_E_ARG, "pool_hint must be 0..128");
-        c->pool_hint = (int)value;
-    } else if (!strcmp(name, "chain_scan")) {
-        if (value < 1 || value > 255) return fail(c, BPE_E_ARG, "chain_scan must be 1..255");
-        c->chain_scan = value;
-    } else if (!strcmp(name, "chain")) {
-        c->chain = value != 0;
-    } else if (!strcmp(name, "lean_chain")) {
-        c->lean_chain = value != 0;
-    } else if (!strcmp(name, "lean_sum")) {
-        c->lean_sum = value != 0;
-    } else if (!strcmp(name, "lean_scan")) {
-        if (value < 1 || value > 1024) return fail(c, BPE_E_ARG, "lean_scan must be 1..1024");
-        c->lean_scan = (int)value;
-    } else if (!strcmp(name, "repack_acc")) {
-        if (value < 0 || value > 10000) return fail(c, BPE_E_ARG, "repack_acc must be 0..10000");
-        c->repack_acc = (int)value;
-    } else if (!strcmp(name, "depth")) {
-        if (value < 0 || value > 64) return fail(c, BPE_E_ARG, "depth must be 0..64");
-        c->depth = (int)value;
-    } else {
-        return fail(c, BPE_E_ARG, "unknown option '%s'", name);
-    }
     return BPE_OK;
 }
 
@@ -309,27 +137,18 @@ static int load_bytes_impl(bpe_ctx *c, const uint8_t *bytes, uint64_t n, const u
             return fail(c, BPE_E_LIMIT, "the weighted chunks stand for >= 2^32 bytes of text (32-bit pair counts)");
     }
     HIPCHK(c, hipSetDevice(c->device));
-    if (n + 16 > c->cap_bytes) {
-        TRY(dev_realloc(c, c->d_bytes, (size_t)n + 16));
-        c->cap_bytes = n + 16;
-    }
+    TRY(grow(c, c->cap_bytes, n + 16, c->d_bytes));
     if (n) TRY(upload_h2d(c, c->d_bytes, bytes, n));
     static const uint64_t zero = 0;
     if (!chunk_offsets) {
         chunk_offsets = &zero;
         n_chunks = 1;
     }
-    if (n_chunks > c->cap_offsets) {
-        TRY(dev_realloc(c, c->d_offsets, (size_t)n_chunks));
-        c->cap_offsets = n_chunks;
-    }
+    TRY(grow(c, c->cap_offsets, n_chunks, c->d_offsets));
     if (n_chunks) TRY(upload_h2d(c, c->d_offsets, chunk_offsets, n_chunks * sizeof(uint64_t)));
     c->weighted = false;
     if (wexp && n_chunks) {
-        if (n_chunks > c->cap_wexp) {
-            TRY(dev_realloc(c, c->d_wexp, (size_t)n_chunks));
-            c->cap_wexp = n_chunks;
-        }
+        TRY(grow(c, c->cap_wexp, n_chunks, c->d_wexp));
         TRY(upload_h2d(c, c->d_wexp, wexp, n_chunks));
         c->weighted = true;
     }
@@ -370,7 +189,7 @@ int bpe_load_ids(bpe_ctx *c, const int32_t *ids, uint64_t n, const uint64_t *chu
     if (n) {
         HIPCHK(c, hipMemcpyAsync(c->d_ids[1], ids, n * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
         hipLaunchKernelGGL(k_load_ids, dim3(grid_for(n, 256, c->num_cus * 8)), dim3(256), 0, c->stream,
-                           (const int32_t *)c->d_ids[1], c->d_ids[0], n);
+                           (const int32_t *)c->d_ids[1].get(), c->d_ids[0], n);
         LAUNCHCHK(c, "k_load_ids");
     }
     static const uint64_t zero = 0;
@@ -378,10 +197,7 @@ int bpe_load_ids(bpe_ctx *c, const int32_t *ids, uint64_t n, const uint64_t *chu
         chunk_offsets = &zero;
         n_chunks = 1;
     }
-    if (n_chunks > c->cap_offsets) {
-        TRY(dev_realloc(c, c->d_offsets, (size_t)n_chunks));
-        c->cap_offsets = n_chunks;
-    }
+    TRY(grow(c, c->cap_offsets, n_chunks, c->d_offsets));
     if (n && n_chunks) {
         HIPCHK(c, hipMemcpyAsync(c->d_offsets, chunk_offsets, n_chunks * sizeof(uint64_t),
                                  hipMemcpyHostToDevice, c->stream));
@@ -408,7 +224,7 @@ int bpe_get_stats(bpe_ctx *c, uint64_t *n_pairs_out) {
     if (!c) return BPE_E_ARG;
     if (!c->have_ids) return fail(c, BPE_E_STATE, "no ids loaded");
     HIPCHK(c, hipSetDevice(c->device));
-    if (!c->d_first) TRY(dev_realloc(c, c->d_first, (size_t)c->vcap * c->vcap));
+    TRY(dev_once(c, c->d_first, (size_t)c->vcap * c->vcap));  // (ensure_table drops it when the table grows)
     TRY(clear_table(c));
     HIPCHK(c, hipMemsetAsync(c->d_first, 0xFF, (size_t)c->vcur * c->vcap * sizeof(uint32_t), c->stream));
     TRY(launch_pair_count(c, true));
@@ -429,14 +245,13 @@ int bpe_read_stats(bpe_ctx *c, int32_t *a, int32_t *b, uint64_t *cnt, uint64_t *
     if (!c) return BPE_E_ARG;
     if (!c->stats_valid) return fail(c, BPE_E_STATE, "bpe_get_stats has not been run on the current ids");
     HIPCHK(c, hipSetDevice(c->device));
-    DevTmp ta, tb, tc, tf;
+    DevPtr<int32_t> da, db;  // this call's scratch, released on every exit path
+    DevPtr<unsigned long long> dc, df;
     const size_t capn = cap ? cap : 1;
-    HIPCHK(c, ta.alloc(capn * 4));
-    HIPCHK(c, tb.alloc(capn * 4));
-    HIPCHK(c, tc.alloc(capn * 8));
-    HIPCHK(c, tf.alloc(capn * 8));
-    int32_t *da = ta.as<int32_t>(), *db = tb.as<int32_t>();
-    unsigned long long *dc = tc.as<unsigned long long>(), *df = tf.as<unsigned long long>();
+    TRY(dev_realloc(c, da, capn));
+    TRY(dev_realloc(c, db, capn));
+    TRY(dev_realloc(c, dc, capn));
+    TRY(dev_realloc(c, df, capn));
     HIPCHK(c, hipMemsetAsync(&c->d_scratch->count, 0, sizeof(unsigned long long), c->stream));
     hipLaunchKernelGGL(k_dump_stats, dim3(c->vcur), dim3(256), 0, c->stream, c->d_mat, c->d_first,
                        c->vcap, c->vcur, da, db, dc, df, (unsigned long long)cap, &c->d_scratch->count);
@@ -511,7 +326,7 @@ int bpe_read_ids(bpe_ctx *c, int32_t *out, uint64_t cap) {
     if (!c->n) return BPE_OK;
     HIPCHK(c, hipSetDevice(c->device));
     // strip flags into the idle ping-pong buffer, then copy out
-    int32_t *tmp = (int32_t *)c->d_ids[c->par ^ 1];
+    int32_t *tmp = (int32_t *)c->d_ids[c->par ^ 1].get();
     hipLaunchKernelGGL(k_strip_flags, dim3(grid_for(c->n, 256, c->num_cus * 8)), dim3(256), 0,
                        c->stream, c->d_ids[c->par], tmp, c->n);
     LAUNCHCHK(c, "k_strip_flags");
@@ -524,9 +339,8 @@ int bpe_read_chunk_starts(bpe_ctx *c, uint64_t *out, uint64_t cap, uint64_t *n_o
     if (!c) return BPE_E_ARG;
     if (!c->have_ids) return fail(c, BPE_E_STATE, "no ids loaded");
     HIPCHK(c, hipSetDevice(c->device));
-    DevTmp t_out;
-    HIPCHK(c, t_out.alloc((cap ? cap : 1) * 8));
-    unsigned long long *d_out = t_out.as<unsigned long long>();
+    DevPtr<unsigned long long> d_out;
+    TRY(dev_realloc(c, d_out, cap ? cap : 1));
     HIPCHK(c, hipMemsetAsync(&c->d_scratch->count, 0, sizeof(unsigned long long), c->stream));
     if (c->n) {
         hipLaunchKernelGGL(k_collect_starts, dim3(grid_for(c->n, 256, c->num_cus * 8)), dim3(256), 0,

@@ -36,8 +36,74 @@ union ScratchWords {
     struct {  // bpe_dp_table_ready (k_dp_table_join): the largest count that does not fit
         unsigned long long other[5], over;
     } dp;
+    unsigned long long words[SCRATCH_WORDS];  // (the whole buffer)
 };
-static_assert(sizeof(ScratchWords) <= SCRATCH_WORDS * sizeof(unsigned long long), "a user's words lie past the buffer");
+static_assert(sizeof(ScratchWords) == SCRATCH_WORDS * sizeof(unsigned long long), "a user's words lie past the buffer");
+
+// What the ctx owns frees itself: device memory, pinned host memory, events.  A buffer added to bpe_ctx is one
+// declaration; bpe_destroy and bpe_create's failure paths have nothing to list.  The owners convert to the plain pointer
+// (kernel arguments, pointer arithmetic, memsets); where a template parameter is deduced from the argument, or in
+// cond ? p : nullptr, say p.get().
+namespace {
+template <typename T>
+struct DevPtr {  // hipMalloc'ed by dev_realloc / dev_once below
+    T *p = nullptr;
+    DevPtr() = default;
+    DevPtr(const DevPtr &) = delete;
+    DevPtr &operator=(const DevPtr &) = delete;
+    ~DevPtr() {
+        if (p) (void)hipFree(p);
+    }
+    operator T *() const { return p; }
+    T *operator->() const { return p; }
+    T *get() const { return p; }
+};
+
+template <typename T>
+struct PinnedPtr {  // hipHostMalloc'ed
+    T *p = nullptr;
+    PinnedPtr() = default;
+    PinnedPtr(const PinnedPtr &) = delete;
+    PinnedPtr &operator=(const PinnedPtr &) = delete;
+    ~PinnedPtr() { (void)release(); }
+    hipError_t release() {
+        T *q = p;
+        p = nullptr;
+        return q ? hipHostFree(q) : hipSuccess;
+    }
+    hipError_t alloc(size_t count, unsigned flags) {  // (the owner is empty)
+        const hipError_t e = hipHostMalloc((void **)&p, count * sizeof(T), flags);
+        if (e != hipSuccess) p = nullptr;
+        return e;
+    }
+    operator T *() const { return p; }
+    T *operator->() const { return p; }
+    T *get() const { return p; }
+};
+
+struct EventList : std::vector<hipEvent_t> {  // the events in it (null entries: not made yet) are destroyed with it
+    using std::vector<hipEvent_t>::vector;
+    EventList() = default;
+    EventList(const EventList &) = delete;
+    EventList &operator=(const EventList &) = delete;
+    ~EventList() {
+        for (hipEvent_t e : *this)
+            if (e) (void)hipEventDestroy(e);
+    }
+};
+
+struct ProfEvList : std::vector<ProfEv> {  // the open profiling intervals, with their events
+    ProfEvList() = default;
+    ProfEvList(const ProfEvList &) = delete;
+    ProfEvList &operator=(const ProfEvList &) = delete;
+    ~ProfEvList() {
+        for (ProfEv &ev : *this) {
+            (void)hipEventDestroy(ev.e0);
+            (void)hipEventDestroy(ev.e1);
+        }
+    }
+};
+}  // namespace
 
 struct bpe_ctx {
     int device = 0;
@@ -47,50 +113,50 @@ struct bpe_ctx {
     std::string err;
 
     // resident input (bpe_load_bytes)
-    uint8_t *d_bytes = nullptr;
+    DevPtr<uint8_t> d_bytes;
     uint64_t nbytes = 0, cap_bytes = 0;
-    uint64_t *d_offsets = nullptr;
+    DevPtr<uint64_t> d_offsets;
     uint64_t n_chunks = 0, cap_offsets = 0;
     bool have_bytes = false;
-    uint8_t *d_wexp = nullptr;  // per chunk: weight exponent (bpe_load_bytes_weighted)
+    DevPtr<uint8_t> d_wexp;  // per chunk: weight exponent (bpe_load_bytes_weighted)
     // sharded chain steps (dp_train_loop): the communicator of the loop in progress, the MIN payload of a tie's first
     // occurrences (DP_KEY_WORDS int64), the SUM payload of a batch's delta (2 dp_kcap vcap + 64 words)
     const struct DpComm *dp_comm = nullptr;
-    long long *d_dp_ckey = nullptr;
-    uint32_t *d_dp_cfold = nullptr;
+    DevPtr<long long> d_dp_ckey;
+    DevPtr<uint32_t> d_dp_cfold;
     uint64_t cap_dp_cfold = 0;
     bool dp_force_comm = false;  // option "dp_force_comm": issue the collectives in a world of one too (tests, launch-cost measurements)
     int dp_kcap = DP_KCAP_DEFAULT;  // option "dp_kcap": most pairs of a sharded step's batch (the SUM payload, 2 dp_kcap S words, grows with it)
-    uint64_t *d_round_lb = nullptr;  // k_load_count: first chunk of every segment of the byte stream
+    DevPtr<uint64_t> d_round_lb;  // k_load_count: first chunk of every segment of the byte stream
     uint64_t cap_round_lb = 0;
     bool fuse_load = true;  // option "fuse_load": the byte stream's first get_stats rides on the widening pass
     uint64_t cap_wexp = 0;
     bool weighted = false;
 
     // id stream
-    uint32_t *d_ids[2] = {nullptr, nullptr};
+    DevPtr<uint32_t> d_ids[2];
     uint64_t cap_ids = 0;
     int par = 0;
     uint64_t n = 0;
     bool have_ids = false;
 
     // pair table
-    uint32_t *d_mat = nullptr, *d_first = nullptr, *d_rowmax = nullptr;
+    DevPtr<uint32_t> d_mat, d_first, d_rowmax;
     uint32_t vcap = 0;  // matrix dimension == row stride
     uint32_t vcur = 0;  // ids in use: [0, vcur)
     bool stats_valid = false;
 
-    DevState *d_st = nullptr;
-    uint64_t *d_tsum = nullptr, *d_tile_off = nullptr;
-    uint8_t *d_tile_sin = nullptr;
-    unsigned long long *d_sup = nullptr;  // streams of many tiles: the transducers of the super-tiles and their prefixes (k_tile_sup)
+    DevPtr<DevState> d_st;
+    DevPtr<uint64_t> d_tsum, d_tile_off;
+    DevPtr<uint8_t> d_tile_sin;
+    DevPtr<unsigned long long> d_sup;  // streams of many tiles: the transducers of the super-tiles and their prefixes (k_tile_sup)
     uint64_t cap_tiles = 0;
-    IterRec *h_rec = nullptr;  // pinned, device-visible
+    PinnedPtr<IterRec> h_rec;  // pinned, device-visible
     int rec_cap = 0;
-    ScratchWords *d_scratch = nullptr;  // SCRATCH_WORDS x u64 counters, by the names above
-    uint32_t *d_delta = nullptr;       // 4 x vcap: decL | decR | incL | incR
-    uint32_t *d_dirty_list = nullptr;  // rows whose rowmax must be recomputed
-    uint32_t *d_dirty_n = nullptr;
+    DevPtr<ScratchWords> d_scratch;  // SCRATCH_WORDS x u64 counters, by the names above
+    DevPtr<uint32_t> d_delta;       // 4 x vcap: decL | decR | incL | incR
+    DevPtr<uint32_t> d_dirty_list;  // rows whose rowmax must be recomputed
+    DevPtr<uint32_t> d_dirty_n;
     int depth = 8;  // iterations the host may run ahead of the device
     int repack_acc = 200;  // option "repack_acc": 0 = re-pack the dense phase's slots when their fill drops below 31/32; N = when the
                          // empty fractions of the sweeps since the last re-pack add up to N/100 of a sweep (what a re-pack costs)
@@ -104,21 +170,21 @@ struct bpe_ctx {
     bool slotted = false;
     uint64_t slot_T = 0;
     int mq = 0;
-    uint32_t *d_meta[2] = {nullptr, nullptr};
-    uint4 *d_hdr[2] = {nullptr, nullptr};  // per slot: first three words, last word
-    uint32_t *d_slot_lens = nullptr;
-    unsigned long long *d_slot_off = nullptr, *d_slot_bsum = nullptr;
-    uint32_t *d_ids2 = nullptr;  // third stream buffer: target of compactions
+    DevPtr<uint32_t> d_meta[2];
+    DevPtr<uint4> d_hdr[2];  // per slot: first three words, last word
+    DevPtr<uint32_t> d_slot_lens;
+    DevPtr<unsigned long long> d_slot_off, d_slot_bsum;
+    DevPtr<uint32_t> d_ids2;  // third stream buffer: target of compactions
     // second slotted form (k_slots2.hip; use_slots == 2, the default)
     bool slot2 = false;                       // the slotted stream currently uses the 32-byte headers
-    SlotHdr *d_hdr2[2] = {nullptr, nullptr};
-    StageRec *d_stage = nullptr;              // staged headers of a sparse pass: stage[t] for slot t
-    uint32_t *d_smask = nullptr;              // [slot / 32] which slots have a staged header
-    uint32_t *d_cand = nullptr;               // candidate slots of a sparse pass (made by k_select)
-    uint32_t *d_idx = nullptr;                // inverted slot index [IDX_H][idx_cap_words] (bucket-major)
-    uint32_t *d_idx_tmp = nullptr;            // group-major image the build kernel writes, transposed into d_idx
-    uint32_t *d_idx_dirty = nullptr;          // [slot / 32]: slots rewritten by a == b passes since the last build
-    uint32_t *d_removed = nullptr;            // [256 * REMOVED_STRIDE] removal counters of a merge pass
+    DevPtr<SlotHdr> d_hdr2[2];
+    DevPtr<StageRec> d_stage;              // staged headers of a sparse pass: stage[t] for slot t
+    DevPtr<uint32_t> d_smask;              // [slot / 32] which slots have a staged header
+    DevPtr<uint32_t> d_cand;               // candidate slots of a sparse pass (made by k_select)
+    DevPtr<uint32_t> d_idx;                // inverted slot index [IDX_H][idx_cap_words] (bucket-major)
+    DevPtr<uint32_t> d_idx_tmp;            // group-major image the build kernel writes, transposed into d_idx
+    DevPtr<uint32_t> d_idx_dirty;          // [slot / 32]: slots rewritten by a == b passes since the last build
+    DevPtr<uint32_t> d_removed;            // [256 * REMOVED_STRIDE] removal counters of a merge pass
     uint64_t idx_cap_words = 0;               // index groups allocated
     uint64_t idx_cap_rows = 0;                // ... and buckets (rows): those of the geometry the index was allocated in
     bool idx_rebuild = false;                 // an a == b merge went by: rebuild before the next pass
@@ -146,7 +212,7 @@ struct bpe_ctx {
     int lean_chain = 1;                       // option "lean_chain": 1 = tied pairs are merged off the list one selection made (k_sel_lean), 0 = every iteration selects
     int chain_dense = 1;                      // option "chain_dense": chain steps from the second merge on -- dense passes, LDS delta tables, up to CH_KDENSE
                                               // pairs per sweep -- while every id is below LDSD_CAP and the index does not exist yet
-    unsigned long long *d_chain_req = nullptr;  // the request / answer words between the deciding and the scanning workgroups of a chain step's selection (k_pool.hip)
+    DevPtr<unsigned long long> d_chain_req;  // the request / answer words between the deciding and the scanning workgroups of a chain step's selection (k_pool.hip)
     int ts = TILE2_MAX;                       // ids per slot of the second slotted form as the stream stands: 1024 (kernels of namespace bpe_g4)
                                               // or 256 (bpe_g1) -- see GK below
     int small_slots = 1;                      // option "small_slots": re-pack into 256-id slots when the inverted index is first built (a large
@@ -160,20 +226,20 @@ struct bpe_ctx {
                                               // selection -> published batch -> merge pass -> grid barrier -> table update) instead of three.
                                               // Measured SLOWER than the three launches (this part overlaps a dependent launch's
                                               // ramp with its predecessor's tail -- median gap 0.0 us -- and a fence-free grid barrier is 3.8 us): off
-    unsigned long long *d_step_pub = nullptr; // ... its published line (STEP_PUB_WORDS granules)
-    uint32_t *d_step_bar = nullptr;           // ... its grid-barrier counter (only ever grows; zeroed when a train() begins)
+    DevPtr<unsigned long long> d_step_pub; // ... its published line (STEP_PUB_WORDS granules)
+    DevPtr<uint32_t> d_step_bar;           // ... its grid-barrier counter (only ever grows; zeroed when a train() begins)
     uint32_t step_bar_target = 0;             // ... and what it will read once every launch enqueued so far is through its barrier
     // encode as a replay of training (api_encode.hip): the loop's selections are the merges of d_forced, in order
     bool forced = false;
-    int32_t *d_forced = nullptr;
+    DevPtr<int32_t> d_forced;
     uint64_t cap_forced = 0;
     int enc_replay = 1;                       // option "enc_replay": one giant chunk (BasicTokenizer.encode) is encoded by replaying its merge
                                               // list through the training engine (0: the stream-wide rounds)
     // host -> device uploads of large caller buffers (upload_h2d below): a ring of pinned staging buffers filled by several
     // host threads while the copy engine drains the ones before (option "pinned_upload": 0 = plain hipMemcpyAsync)
     int pinned_upload = 1;
-    uint8_t *h_stage = nullptr;
-    hipEvent_t ev_stage[4] = {nullptr, nullptr, nullptr, nullptr};
+    PinnedPtr<uint8_t> h_stage;
+    EventList ev_stage = EventList(4);       // (null until the ring is made)
     bool stage_busy[4] = {false, false, false, false};  // a copy out of / into the buffer was enqueued: wait for its event before the buffer is touched again
     uint64_t n_fused = 0;                     // chain steps of the last train() that were one launch
     int chain_aa = 1;                         // option "chain_aa": a sparse chain step on 256-id slots whose order is headed by a pair with a == b merges
@@ -186,21 +252,21 @@ struct bpe_ctx {
     int chain_hash_kmin = 0;                  // option "chain_hash_kmin": the smallest batch whose merge pass uses the pair look-up table (0: the
                                               // kernels' own, 2); 32 = never: every position is compared with every pair (the exact fall-back)
     uint64_t n_shared_first = 0;              // chain steps of the last train() whose batch held a first token twice
-    unsigned long long *d_step_stamps = nullptr;  // debug (env BPE_STEP_STAMPS=file): clock stamps of its phases, dumped when train() ends
+    DevPtr<unsigned long long> d_step_stamps;  // debug (env BPE_STEP_STAMPS=file): clock stamps of its phases, dumped when train() ends
     int pool_hint = 0;                        // option "pool_hint": a rebuild is announced when fewer untouched entries than this are left (0: the step's cap)
-    PoolEnt *d_pool = nullptr;                // ... its entries (PL_CAP) and the pairs a rebuild gathers (counter, pad, PL_GATHER x {pair, count})
-    uint32_t *d_pool_gather = nullptr;
+    DevPtr<PoolEnt> d_pool;                // ... its entries (PL_CAP) and the pairs a rebuild gathers (counter, pad, PL_GATHER x {pair, count})
+    DevPtr<uint32_t> d_pool_gather;
     int chain_scan = 127;                     // option "chain_scan": workgroups that re-scan flagged rows in a chain step's FULL selection (a level of
                                               // n merges leaves ~3 n rows to re-scan, one 128 KB row per workgroup at a time)
     int chain = 1;                            // option "chain": 1 = chain steps (k_chain.hip: the tied pairs kept as a list, batches of
                                               // token-disjoint pairs merged in one pass) instead of lean iterations, wherever those would run with the index live
-    StepRec *h_srec = nullptr;                // pinned ring of step records (STEP_RING entries)
+    PinnedPtr<StepRec> h_srec;                // pinned ring of step records (STEP_RING entries)
     uint64_t n_steps = 0, n_full = 0, n_chained = 0;  // chain steps of the last train(), those that selected, merges that needed no selection
     int lean_sum = 1;                         // option "lean_sum": 1 = k_sel_lean (selection from the table update's per-wave records) whenever they are current
-    uint4 *d_lean_sum = nullptr;              // [4][LEAN_SUM_CAP] those records (k_lean.hip)
+    DevPtr<uint4> d_lean_sum;              // [4][LEAN_SUM_CAP] those records (k_lean.hip)
     bool sum_valid = false;                   // ... describe the table as it stands (the last iteration enqueued was a lean one)
-    uint32_t *d_dbits = nullptr;              // [DBITS_WORDS] rows a lean table update flagged for re-scanning
-    unsigned long long *d_lean_res = nullptr; // row maxima on their way to the deciding workgroup of k_rowsel_lean: 2 words per item
+    DevPtr<uint32_t> d_dbits;              // [DBITS_WORDS] rows a lean table update flagged for re-scanning
+    DevPtr<unsigned long long> d_lean_res; // row maxima on their way to the deciding workgroup of k_rowsel_lean: 2 words per item
     uint32_t lean_tag = 0;                    // ... tagged with this launch counter
     bool rows_pending = false;                // a lean table update ran and its rows have not been re-scanned yet
     uint64_t cap_slots = 0;
@@ -209,51 +275,51 @@ struct bpe_ctx {
     bool dp_active = false;  // between bpe_dp_begin and bpe_dp_end
     void *comm = nullptr;    // RCCL communicator (bpe_comm_init), one rank per ctx
     int comm_rank = 0, comm_nranks = 1;
-    uint32_t *d_dp_folded = nullptr, *d_dp_table = nullptr;
-    long long *d_dp_key = nullptr;
+    DevPtr<uint32_t> d_dp_folded, d_dp_table;
+    DevPtr<long long> d_dp_key;
     uint64_t dp_cur_len = 0;
     bool dp_sparse = false;                   // second slotted form: this iteration's a != b pass is a sparse one
     uint32_t dp_dl = 0;                       // ... and the delta layout its kernels used
     std::vector<uint8_t> dp_flip;             // ... and which iterations flipped the header arrays
     int merge_impl = 0;  // 0 three-pass | 1 single-pass (two-level decoupled look-back)
-    unsigned long long *d_desc = nullptr;   // look-back descriptors, one per tile
-    unsigned long long *d_gdesc = nullptr;  // ... and one per group of 64 tiles
+    DevPtr<unsigned long long> d_desc;   // look-back descriptors, one per tile
+    DevPtr<unsigned long long> d_gdesc;  // ... and one per group of 64 tiles
     uint64_t cap_desc = 0;
     uint32_t epoch = 0;
     uint32_t lb_tune = 1;  // bits 0..7: s_sleep(8) units between polls; bit 8: measurement-only 'no wait'
 
     // encode scratch (grow-only)
-    uint32_t *d_enc_tmp = nullptr, *d_enc_len = nullptr;
-    int32_t *d_enc_out = nullptr;
-    unsigned long long *d_enc_off = nullptr, *d_enc_bsum = nullptr, *d_enc_long = nullptr;
-    unsigned long long *d_enc_huge = nullptr;  // chunks of more than ENC_LONG_TOP bytes: the stream-wide rounds' (k_enc_long hands them on)
+    DevPtr<uint32_t> d_enc_tmp, d_enc_len;
+    DevPtr<int32_t> d_enc_out;
+    DevPtr<unsigned long long> d_enc_off, d_enc_bsum, d_enc_long;
+    DevPtr<unsigned long long> d_enc_huge;  // chunks of more than ENC_LONG_TOP bytes: the stream-wide rounds' (k_enc_long hands them on)
     int enc_long = 1;                          // option "enc_long": chunks of ENC_LMAX + 1 .. ENC_LONG_TOP bytes are encoded on the device, one wave
                                                // per chunk (k_enc_long); 0 = all of them through the stream-wide rounds (round 4's path, a cross-check)
-    unsigned long long *d_ht_keys = nullptr;
-    uint32_t *d_ht_vals = nullptr;
-    int32_t *d_merge_ids = nullptr;
+    DevPtr<unsigned long long> d_ht_keys;
+    DevPtr<uint32_t> d_ht_vals;
+    DevPtr<int32_t> d_merge_ids;
     uint64_t cap_enc_n = 0, cap_enc_chunks = 0, cap_ht = 0, cap_merge_ids = 0;
     // the chunk cache of bpe_encode_batch (k_encode.hip): hash table + per chunk its slot, then its owner
-    EncEntry *d_enc_tab = nullptr;
-    uint32_t *d_enc_rep = nullptr;  // per chunk: its slot
-    uint8_t *d_enc_mid = nullptr;             // pass 2's work list: lane numbers, packed per workgroup of pass 1 (k_encode.hip)
-    uint32_t *d_enc_midn = nullptr;           // ... and how many per workgroup
+    DevPtr<EncEntry> d_enc_tab;
+    DevPtr<uint32_t> d_enc_rep;  // per chunk: its slot
+    DevPtr<uint8_t> d_enc_mid;             // pass 2's work list: lane numbers, packed per workgroup of pass 1 (k_encode.hip)
+    DevPtr<uint32_t> d_enc_midn;           // ... and how many per workgroup
     uint64_t cap_enc_tab = 0;
     int enc_cache = 1;  // option "enc_cache": 0 = encode every chunk on its own
     int enc_chain = 1;  // option "enc_chain": 1 = output offsets and placement in one chained pass (k_enc_place_chained)
     int enc_hash_bits = 0;  // option "enc_hash_bits" (tests): keep only this many bits of the chunk hash (0 = all 64)
 
     // decode (grow-only): vocab table, then ids / lengths / offsets / bytes of the last batch
-    uint8_t *d_dec_blob = nullptr, *d_dec_out = nullptr;
-    unsigned long long *d_dec_voff = nullptr, *d_dec_off = nullptr, *d_dec_bsum = nullptr;
-    int32_t *d_dec_ids = nullptr;
-    uint32_t *d_dec_len = nullptr;
+    DevPtr<uint8_t> d_dec_blob, d_dec_out;
+    DevPtr<unsigned long long> d_dec_voff, d_dec_off, d_dec_bsum;
+    DevPtr<int32_t> d_dec_ids;
+    DevPtr<uint32_t> d_dec_len;
     uint64_t cap_dec_blob = 0, cap_dec_voff = 0, cap_dec_n = 0, cap_dec_out = 0;
     uint32_t dec_V = 0;
     bool dec_have_vocab = false, dec_have_result = false;
     uint64_t dec_n = 0, dec_total = 0;
     // bpe_decode_batch_resident: ids outside [0, dec_V_dense) that decode (sorted; entry j = table index dec_V_dense + j)
-    int32_t *d_dec_sparse = nullptr;
+    DevPtr<int32_t> d_dec_sparse;
     uint64_t cap_dec_sparse = 0;
     uint32_t dec_V_dense = 0, dec_n_sparse = 0;
     int dec_copy = 1;        // option "dec_copy": 1 = k_decode_copy_staged (LDS window, 16-byte stores) | 0 = k_decode_copy (one token per lane)
@@ -264,8 +330,8 @@ struct bpe_ctx {
     int rows_stage = 1024;   // option "rows_stage": document starts a tile stages in LDS (0: every lane searches global memory, the cross-check form)
     // bpe_token_spans_resident (k_spans.hip): leads | cont << 31 of every table entry, made on the device by the first
     // call after a bpe_decode_set_vocab; the second scan channel and the documents' bases (grow-only)
-    uint32_t *d_dec_meta = nullptr;
-    unsigned long long *d_spn_off = nullptr, *d_spn_bsum = nullptr, *d_spn_base = nullptr;
+    DevPtr<uint32_t> d_dec_meta;
+    DevPtr<unsigned long long> d_spn_off, d_spn_bsum, d_spn_base;
     uint64_t cap_dec_meta = 0, cap_spn_n = 0, cap_spn_docs = 0;
     bool dec_meta_valid = false;
     int spans_stage = 1024;  // option "spans_stage": document starts a tile stages in LDS (0: every lane searches global memory, the cross-check form)
@@ -273,8 +339,8 @@ struct bpe_ctx {
     // the vocab_size last asked for (grow-only): entry e = id proj_vs + e, ids d_proj_tab[d_proj_toff[e] .. d_proj_toff[e + 1])
     std::vector<int32_t> proj_merges;
     int32_t proj_M = -1;     // -1: no bpe_project_set_merges yet
-    int32_t *d_proj_pass = nullptr, *d_proj_tab = nullptr;
-    uint32_t *d_proj_toff = nullptr;
+    DevPtr<int32_t> d_proj_pass, d_proj_tab;
+    DevPtr<uint32_t> d_proj_toff;
     uint64_t cap_proj_pass = 0, cap_proj_tab = 0, cap_proj_toff = 0;
     uint32_t proj_n_pass = 0;
     int64_t proj_vs = -1;    // the vocab_size the table on the device was made for (-1: none)
@@ -295,8 +361,8 @@ struct bpe_ctx {
     int k1 = 2;       // 0 one atomic per position | 1 LDS hash cache (8-byte slots) | 2 = 1 + dense 16-bit LDS table for byte streams | 3 = 2 with the 4-byte-slot LDS cache for general unweighted streams (measured: no faster, both bound by L2 atomics on cold pairs)
     bool stream_is_bytes = false;  // every id of the current stream is < 256 (fresh from k_widen)
 
-    std::vector<ProfEv> prof_open;
-    std::vector<hipEvent_t> ev_pool;
+    ProfEvList prof_open;
+    EventList ev_pool;
     double prof_ms[BPE_PROF_NKINDS] = {0};
     uint64_t prof_launches[BPE_PROF_NKINDS] = {0};
     uint64_t prof_bytes[BPE_PROF_NKINDS] = {0};
@@ -339,34 +405,43 @@ int fail(bpe_ctx *c, int code, const char *fmt, ...) {
         if (rc_ != BPE_OK) return rc_; \
     } while (0)
 
-// scratch device allocation of one call, released on every exit path
-struct DevTmp {
-    void *p = nullptr;
-    DevTmp() = default;
-    DevTmp(const DevTmp &) = delete;
-    DevTmp &operator=(const DevTmp &) = delete;
-    ~DevTmp() {
-        if (p) (void)hipFree(p);
-    }
-    hipError_t alloc(size_t bytes) { return hipMalloc(&p, bytes ? bytes : 1); }
-    template <typename T>
-    T *as() const { return (T *)p; }
-};
-
-struct EventList {
-    std::vector<hipEvent_t> v;
-    ~EventList() {
-        for (hipEvent_t e : v)
-            if (e) (void)hipEventDestroy(e);
-    }
-};
-
+// ---- allocation: every hipMalloc of the library is in the two functions below -----------------------------------
+// resize: p holds `count` elements, contents undefined (a call's scratch is a local DevPtr filled the same way).  After a
+// failure p is null.
 template <typename T>
-int dev_realloc(bpe_ctx *c, T *&p, size_t count) {
+int dev_realloc(bpe_ctx *c, DevPtr<T> &p, size_t count) {
     if (p) HIPCHK(c, hipFree(p));
-    p = nullptr;
-    if (count) HIPCHK(c, hipMalloc((void **)&p, count * sizeof(T)));
+    p.p = nullptr;
+    if (count) HIPCHK(c, hipMalloc((void **)&p.p, count * sizeof(T)));
     return BPE_OK;
+}
+
+// allocate once: a buffer whose size never changes is made by the first call that wants it (zero: and cleared then, on
+// the ctx's stream)
+template <typename T>
+int dev_once(bpe_ctx *c, DevPtr<T> &p, size_t count, bool zero = false) {
+    if (p) return BPE_OK;
+    HIPCHK(c, hipMalloc((void **)&p.p, count * sizeof(T)));
+    if (zero) HIPCHK(c, hipMemsetAsync(p, 0, count * sizeof(T), c->stream));
+    return BPE_OK;
+}
+
+// The grow rule of every buffer group sized by one capacity word: the group is replaced when `need` exceeds the word,
+// the word reads 0 while that goes on and gets its new value only after every member is allocated -- so after a failed
+// allocation the next call, whatever its size, allocates again instead of handing a null pointer to a kernel.
+// members() allocates them (dev_realloc each) and returns a code.
+template <typename Cap, typename F>
+int grow_group(Cap &cap, uint64_t need, F &&members) {
+    if (need <= (uint64_t)cap) return BPE_OK;
+    cap = 0;
+    TRY(members());
+    cap = (Cap)need;
+    return BPE_OK;
+}
+// ... a group of one buffer, of `need` elements
+template <typename Cap, typename T>
+int grow(bpe_ctx *c, Cap &cap, uint64_t need, DevPtr<T> &p) {
+    return grow_group(cap, need, [&]() -> int { return dev_realloc(c, p, (size_t)need); });
 }
 
 inline uint64_t ntiles_of(uint64_t n) { return (n + TILE - 1) / TILE; }
@@ -379,15 +454,15 @@ int scan_lengths(bpe_ctx *c, const uint32_t *len, uint64_t n, unsigned long long
 int ensure_ids(bpe_ctx *c, uint64_t n) {
     // capacity padded so every tile load (and the +1 halo word) is in bounds
     const uint64_t need = (ntiles_of(n) + 2) * TILE;
-    if (need > c->cap_ids) {
+    TRY(grow_group(c->cap_ids, need, [&]() -> int {
         TRY(dev_realloc(c, c->d_ids[0], need));
         TRY(dev_realloc(c, c->d_ids[1], need));
         TRY(dev_realloc(c, c->d_ids2, need));
-        c->cap_ids = need;
-    }
+        return BPE_OK;
+    }));
     const uint64_t nt = ntiles_of(n) + 1;
     const uint64_t nt2 = (TILE / TILE2_MIN) * nt + 4;  // slots of the second slotted form (as few as TILE2_MIN ids each)
-    if (nt > c->cap_tiles) {
+    return grow_group(c->cap_tiles, nt, [&]() -> int {
         TRY(dev_realloc(c, c->d_tsum, nt));
         TRY(dev_realloc(c, c->d_tile_off, nt));
         TRY(dev_realloc(c, c->d_tile_sin, nt));
@@ -409,9 +484,8 @@ int ensure_ids(bpe_ctx *c, uint64_t n) {
         TRY(dev_realloc(c, c->d_gdesc, nt / 64 + 2));
         HIPCHK(c, hipMemsetAsync(c->d_desc, 0, nt2 * sizeof(unsigned long long), c->stream));
         HIPCHK(c, hipMemsetAsync(c->d_gdesc, 0, (nt / 64 + 2) * sizeof(unsigned long long), c->stream));
-        c->cap_tiles = nt;
-    }
-    return BPE_OK;
+        return BPE_OK;
+    });
 }
 
 int ensure_table(bpe_ctx *c, uint32_t v) {
@@ -419,47 +493,38 @@ int ensure_table(bpe_ctx *c, uint32_t v) {
     if (v <= c->vcap) return BPE_OK;
     uint32_t nv = std::max<uint32_t>(v, 256);
     nv = (nv + 63) & ~63u;  // rows stay 256 B aligned
+    c->vcap = 0;  // (the grow rule: the new value once every member is allocated)
     TRY(dev_realloc(c, c->d_mat, (size_t)nv * nv));
     TRY(dev_realloc(c, c->d_rowmax, (size_t)nv * 2));  // interleaved: rowmax[2x] = max of row x, rowmax[2x + 1] = its column (or ROWARG_MULTI)
     TRY(dev_realloc(c, c->d_delta, (size_t)nv * 4 * DELTA_REPL + 256 * DELTA_SKEW));  // (+ the skew of up to 256 replicas)
     TRY(dev_realloc(c, c->d_dirty_list, (size_t)nv));
-    if (!c->d_dirty_n) HIPCHK(c, hipMalloc((void **)&c->d_dirty_n, sizeof(uint32_t)));
-    if (!c->d_dbits) {
-        HIPCHK(c, hipMalloc((void **)&c->d_dbits, DBITS_WORDS * sizeof(uint32_t)));
-        HIPCHK(c, hipMemsetAsync(c->d_dbits, 0, DBITS_WORDS * sizeof(uint32_t), c->stream));
-    }
+    TRY(dev_once(c, c->d_dirty_n, 1));
+    TRY(dev_once(c, c->d_dbits, DBITS_WORDS, true));
     TRY(dev_realloc(c, c->d_lean_res, 2 * ((size_t)nv + 8)));
-    if (!c->d_lean_sum) HIPCHK(c, hipMalloc((void **)&c->d_lean_sum, 4 * (size_t)LEAN_SUM_CAP * sizeof(uint4)));
+    TRY(dev_once(c, c->d_lean_sum, 4 * (size_t)LEAN_SUM_CAP));
     HIPCHK(c, hipMemsetAsync(c->d_lean_res, 0, 2 * ((size_t)nv + 8) * sizeof(unsigned long long), c->stream));
-    if (!c->d_removed) {
-        HIPCHK(c, hipMalloc((void **)&c->d_removed, 256 * REMOVED_STRIDE * sizeof(uint32_t)));
-        HIPCHK(c, hipMemsetAsync(c->d_removed, 0, 256 * REMOVED_STRIDE * sizeof(uint32_t), c->stream));
-    }
+    TRY(dev_once(c, c->d_removed, 256 * REMOVED_STRIDE, true));
     HIPCHK(c, hipMemsetAsync(c->d_delta, 0, ((size_t)nv * 4 * DELTA_REPL + 256 * DELTA_SKEW) * sizeof(uint32_t), c->stream));
     HIPCHK(c, hipMemsetAsync(c->d_dirty_n, 0, sizeof(uint32_t), c->stream));
     // rows beyond the ids in use read as "no pair" (a deferred lean iteration's no-op successors run
     // k_select with a vocabulary the table has not reached yet)
     HIPCHK(c, hipMemsetAsync(c->d_rowmax, 0, (size_t)nv * 2 * sizeof(uint32_t), c->stream));
-    if (c->d_first) {
-        HIPCHK(c, hipFree(c->d_first));
-        c->d_first = nullptr;
-    }
+    if (c->d_first) TRY(dev_realloc(c, c->d_first, 0));
     c->vcap = nv;
     c->stats_valid = false;
     return BPE_OK;
 }
 
 int ensure_rec(bpe_ctx *c, int n) {
-    if (n <= c->rec_cap) return BPE_OK;
-    if (c->h_rec) HIPCHK(c, hipHostFree(c->h_rec));
-    c->h_rec = nullptr;
-    HIPCHK(c, hipHostMalloc((void **)&c->h_rec, sizeof(IterRec) * (size_t)n, hipHostMallocMapped));
-    c->rec_cap = n;
-    return BPE_OK;
+    return grow_group(c->rec_cap, (uint64_t)std::max(n, 0), [&]() -> int {
+        HIPCHK(c, c->h_rec.release());
+        HIPCHK(c, c->h_rec.alloc((size_t)n, hipHostMallocMapped));
+        return BPE_OK;
+    });
 }
 
 int ensure_srec(bpe_ctx *c) {
-    if (!c->h_srec) HIPCHK(c, hipHostMalloc((void **)&c->h_srec, sizeof(StepRec) * STEP_RING, hipHostMallocMapped));
+    if (!c->h_srec) HIPCHK(c, c->h_srec.alloc(STEP_RING, hipHostMallocMapped));
     memset(c->h_srec, 0, sizeof(StepRec) * STEP_RING);
     return BPE_OK;
 }
@@ -546,12 +611,9 @@ int start_from_bytes(bpe_ctx *c, bool count = false) {
     TRY(ensure_ids(c, n));
     if (count) {
         const uint64_t segs = (n + LC_SEG - 1) / LC_SEG;
-        if (segs + 2 > c->cap_round_lb) {
-            TRY(dev_realloc(c, c->d_round_lb, (size_t)segs + 2));
-            c->cap_round_lb = segs + 2;
-        }
+        TRY(grow(c, c->cap_round_lb, segs + 2, c->d_round_lb));
         TRY(prof_begin(c, BPE_PROF_PAIR_COUNT, 4 * n));
-        const uint64_t *off = c->n_chunks ? c->d_offsets : nullptr;
+        const uint64_t *off = c->n_chunks ? c->d_offsets.get() : nullptr;
         if (off) {
             hipLaunchKernelGGL(k_seg_lb, dim3((unsigned)((segs + 256) / 256)), dim3(256), 0, c->stream, off,
                                (uint64_t)c->n_chunks, segs, c->d_round_lb);
@@ -839,7 +901,7 @@ int launch_merge(bpe_ctx *c, uint32_t newid, int iter, IterRec *rec, bool with_d
     if (nt > (uint64_t)c->scan_sup_min) {  // many tiles: three small launches instead of one workgroup's serial walk
         static_assert(sizeof(TS) == 24, "a TS is three 8-byte words");
         const uint64_t nsup = (nt + SUP_TILES - 1) / SUP_TILES;
-        TS *ssum = reinterpret_cast<TS *>(c->d_sup), *spre = ssum + (nt / SUP_TILES + 2);
+        TS *ssum = reinterpret_cast<TS *>(c->d_sup.get()), *spre = ssum + (nt / SUP_TILES + 2);
         hipLaunchKernelGGL(k_tile_sup, dim3((unsigned)nsup), dim3(SUP_TILES), 0, c->stream, c->d_tsum, nt, c->d_st, c->par, ssum);
         hipLaunchKernelGGL(k_tile_scan_sup, dim3(1), dim3(1024), 0, c->stream, ssum, nsup, spre, c->d_st, c->par, rec, iter,
                            c->d_ids[c->par], c->d_dirty_n);
@@ -904,7 +966,7 @@ int slots_leave(bpe_ctx *c) {
                            c->d_ids[1], c->d_meta[c->mq], c->d_slot_off, c->d_ids2);
         LAUNCHCHK(c, "k_slot_compact");
     }
-    std::swap(c->d_ids[0], c->d_ids2);
+    std::swap(c->d_ids[0].p, c->d_ids2.p);
     if (c->par != 0) {
         hipLaunchKernelGGL(k_move_n, dim3(1), dim3(1), 0, c->stream, c->d_st, c->par, 0);
         LAUNCHCHK(c, "k_move_n");
@@ -954,16 +1016,15 @@ int index_build(bpe_ctx *c) {
     // (rows = buckets of the geometry the stream is in: 32 Ki for 1024-id slots, 8 Ki for 256-id slots -- which has four
     // times the slots, hence four times the words per row: the same bytes either way)
     if (nwords + 4 > c->idx_cap_words || idx_h(c) > c->idx_cap_rows) {
-        if (c->d_idx) HIPCHK(c, hipFree(c->d_idx));
-        if (c->d_idx_dirty) HIPCHK(c, hipFree(c->d_idx_dirty));
-        c->d_idx = c->d_idx_dirty = nullptr;
+        // (two capacity words, and all three buffers released before the first is made anew: the grow rule by hand)
         const uint64_t cap = (nwords + 4 + 63) / 64 * 64;  // row stride: 16-byte aligned rows, a padded tail
-        if (c->d_idx_tmp) HIPCHK(c, hipFree(c->d_idx_tmp));
-        c->d_idx_tmp = nullptr;
         c->idx_cap_words = c->idx_cap_rows = 0;
-        HIPCHK(c, hipMalloc((void **)&c->d_idx, cap * idx_h(c) * sizeof(uint32_t)));
-        HIPCHK(c, hipMalloc((void **)&c->d_idx_tmp, cap * idx_h(c) * sizeof(uint32_t)));
-        HIPCHK(c, hipMalloc((void **)&c->d_idx_dirty, cap * sizeof(uint32_t)));
+        TRY(dev_realloc(c, c->d_idx, 0));
+        TRY(dev_realloc(c, c->d_idx_dirty, 0));
+        TRY(dev_realloc(c, c->d_idx_tmp, 0));
+        TRY(dev_realloc(c, c->d_idx, cap * idx_h(c)));
+        TRY(dev_realloc(c, c->d_idx_tmp, cap * idx_h(c)));
+        TRY(dev_realloc(c, c->d_idx_dirty, cap));
         c->idx_cap_words = cap;
         c->idx_cap_rows = idx_h(c);
     }
@@ -1008,7 +1069,7 @@ int slots2_leave(bpe_ctx *c) {
                            c->d_ids[1], c->d_hdr2[c->mq], T, c->d_slot_off, c->d_ids2);
         LAUNCHCHK(c, "k_slot2_compact");
     }
-    std::swap(c->d_ids[0], c->d_ids2);
+    std::swap(c->d_ids[0].p, c->d_ids2.p);
     if (c->par != 0) {
         hipLaunchKernelGGL(k_move_n, dim3(1), dim3(1), 0, c->stream, c->d_st, c->par, 0);
         LAUNCHCHK(c, "k_move_n");
@@ -1233,6 +1294,41 @@ int launch_lean(bpe_ctx *c, uint32_t newid, int iter, IterRec *rec, bool use_ind
     return BPE_OK;
 }
 
+// what a chain step keeps between its launches, made by the first step that runs (fused: and what the one-launch step adds)
+int ensure_chain_buffers(bpe_ctx *c, bool fused) {
+    TRY(dev_once(c, c->d_chain_req, PL_REQ_WORDS, true));
+    TRY(dev_once(c, c->d_pool, 3 * PL_CAP + 128, true));  // (+ a sharded selection's hand-over: k_pool_sel -> k_pool_sel_dp)
+    TRY(dev_once(c, c->d_pool_gather, 2 + 2 * PL_GATHER, true));
+    if (!fused) return BPE_OK;
+    TRY(dev_once(c, c->d_step_pub, 64, true));
+    if (!c->d_step_bar) c->step_bar_target = 0;
+    return dev_once(c, c->d_step_bar, 256 / sizeof(uint32_t), true);
+}
+
+// The merge pass's arguments of a chain step, for the three launches and for the one launch alike: the one-launch step
+// runs only with the index live, outside a sharded loop and never dense (`fused` in launch_chain_step), which is where
+// the conditions below come out as what it wants -- no hdr_out, the index, `removed` without the sharded term.
+AbArgs chain_ab_args(const bpe_ctx *c, uint32_t T, uint32_t dl, bool dense, uint32_t *removed) {
+    AbArgs A;
+    A.b0 = c->d_ids[0];
+    A.b1 = c->d_ids[1];
+    A.hdr_in = c->d_hdr2[c->mq];
+    A.hdr_out = dense ? c->d_hdr2[c->mq ^ 1].get() : nullptr;
+    A.stage = c->d_stage;
+    A.smask = c->d_smask;
+    A.T = T;
+    A.st = c->d_st;
+    A.newid = 0;  // (the device knows: st->bz0, or the one-launch step's published line)
+    A.delta = c->d_delta;
+    A.vcap = dl;
+    A.idx = c->idx_live ? c->d_idx.get() : nullptr;
+    A.istride = (uint32_t)c->idx_cap_words;
+    A.cand = nullptr;
+    A.removed = removed;
+    A.dirty_n = c->d_dirty_n;
+    return A;
+}
+
 // A chain step (k_chain.hip): selection or list look-ups, one merge pass for the whole batch, table update.
 // zhi: the largest token id the step can make (the device counts the merges; the host only knows a bound).
 // records: the last launch that touched the pair table was a k_apply_chain.
@@ -1257,16 +1353,7 @@ int launch_chain_step(bpe_ctx *c, uint32_t step, uint32_t zhi, bool use_index, b
     // ordered wrongly: nobody orders it, every rank reports "no occurrence" and the general path decides)
     if (dense && c->dp_comm) C.T = 0;
     (void)records;
-    if (!c->d_chain_req) {
-        HIPCHK(c, hipMalloc((void **)&c->d_chain_req, PL_REQ_WORDS * sizeof(unsigned long long)));
-        HIPCHK(c, hipMemsetAsync(c->d_chain_req, 0, PL_REQ_WORDS * sizeof(unsigned long long), c->stream));
-    }
-    if (!c->d_pool) {
-        HIPCHK(c, hipMalloc((void **)&c->d_pool, (3 * PL_CAP + 128) * sizeof(PoolEnt)));  // (+ a sharded selection's hand-over: k_pool_sel -> k_pool_sel_dp)
-        HIPCHK(c, hipMalloc((void **)&c->d_pool_gather, (2 + 2 * PL_GATHER) * sizeof(uint32_t)));
-        HIPCHK(c, hipMemsetAsync(c->d_pool, 0, (3 * PL_CAP + 128) * sizeof(PoolEnt), c->stream));
-        HIPCHK(c, hipMemsetAsync(c->d_pool_gather, 0, (2 + 2 * PL_GATHER) * sizeof(uint32_t), c->stream));
-    }
+    TRY(ensure_chain_buffers(c, fused));
     // sharded training (dp_train_loop, api_rccl.hip): the step's two collectives sit between its launches -- a tie's
     // first occurrences (MIN) before the batch is formed, the batch's delta (SUM) before the table update: k_pool_sel
     // leaves the local first occurrences of the entries it must order, k_pool_sel_dp finishes the selection from the
@@ -1288,18 +1375,12 @@ int launch_chain_step(bpe_ctx *c, uint32_t step, uint32_t zhi, bool use_index, b
     // the one-launch step and forced replays keep distinct first tokens)
     const bool share_first = c->chain_share_first && !fused && !c->forced && !dp;
     const uint32_t sel_flags = (aa_on ? (uint32_t)PSF_AA : 0u) | (share_first ? (uint32_t)PSF_SHARE_FIRST : 0u) | ((uint32_t)c->chain_hash_kmin << 8);
+    // (an unweighted stream: a != b merges remove exactly `count` ids -- no removal counters, one atomic less per site;
+    // sharded steps keep them: the count is the GLOBAL one, the ids removed are this shard's)
+    uint32_t *const removed = (c->weighted || dp || !c->count_is_removed) ? c->d_removed.get() : nullptr;
+    const uint32_t nwords = (T + 31) / 32;
     if (fused) {
         // ---- the whole step as ONE launch (k_step.hip) ----------------------------------------------------------------
-        if (!c->d_step_pub) {
-            HIPCHK(c, hipMalloc((void **)&c->d_step_pub, 64 * sizeof(unsigned long long)));
-            HIPCHK(c, hipMemsetAsync(c->d_step_pub, 0, 64 * sizeof(unsigned long long), c->stream));
-        }
-        if (!c->d_step_bar) {
-            HIPCHK(c, hipMalloc((void **)&c->d_step_bar, 256));
-            HIPCHK(c, hipMemsetAsync(c->d_step_bar, 0, 256, c->stream));
-            c->step_bar_target = 0;
-        }
-        const uint32_t nwords = (T + 31) / 32;
         StepArgs S;
         S.rowmax = c->d_rowmax;
         S.mat = c->d_mat;
@@ -1315,24 +1396,7 @@ int launch_chain_step(bpe_ctx *c, uint32_t step, uint32_t zhi, bool use_index, b
         S.pool = c->d_pool;
         S.gather = c->d_pool_gather;
         S.hint_below = hint_below;
-        AbArgs &A = S.A;
-        A.b0 = c->d_ids[0];
-        A.b1 = c->d_ids[1];
-        A.hdr_in = c->d_hdr2[c->mq];
-        A.hdr_out = nullptr;
-        A.stage = c->d_stage;
-        A.smask = c->d_smask;
-        A.T = T;
-        A.st = c->d_st;
-        A.newid = 0;  // (the device knows: the published line)
-        A.delta = c->d_delta;
-        A.vcap = dl;
-        A.idx = c->d_idx;
-        A.istride = (uint32_t)c->idx_cap_words;
-        A.cand = nullptr;
-        uint32_t *const removed = (c->weighted || !c->count_is_removed) ? c->d_removed : nullptr;
-        A.removed = removed;
-        A.dirty_n = c->d_dirty_n;
+        S.A = chain_ab_args(c, T, dl, dense, removed);
         S.idx_dirty = c->d_idx_dirty;
         S.use_index = 1u | (c->chain_prefetch ? 2u : 0u);
         // the grid: what the merge pass wants, what the table update needs (a token per thread), the scanning workgroups --
@@ -1390,27 +1454,7 @@ int launch_chain_step(bpe_ctx *c, uint32_t step, uint32_t zhi, bool use_index, b
         LAUNCHCHK(c, "k_pool_sel_dp");
     }
     TRY(prof_end(c));
-    AbArgs A;
-    A.b0 = c->d_ids[0];
-    A.b1 = c->d_ids[1];
-    A.hdr_in = c->d_hdr2[c->mq];
-    A.hdr_out = dense ? c->d_hdr2[c->mq ^ 1] : nullptr;
-    A.stage = c->d_stage;
-    A.smask = c->d_smask;
-    A.T = T;
-    A.st = c->d_st;
-    A.newid = 0;  // (the device knows: st->bz0)
-    A.delta = c->d_delta;
-    A.vcap = dl;
-    A.idx = c->idx_live ? c->d_idx : nullptr;
-    A.istride = (uint32_t)c->idx_cap_words;
-    A.cand = nullptr;
-    // (an unweighted stream: a != b merges remove exactly `count` ids -- no removal counters, one atomic less per site;
-    // sharded steps keep them: the count is the GLOBAL one, the ids removed are this shard's)
-    uint32_t *const removed = (c->weighted || dp || !c->count_is_removed) ? c->d_removed : nullptr;
-    A.removed = removed;
-    A.dirty_n = c->d_dirty_n;
-    const uint32_t nwords = (T + 31) / 32;
+    const AbArgs A = chain_ab_args(c, T, dl, dense, removed);
     TRY(prof_begin(c, BPE_PROF_MERGE, 0));
     if (dense) {
         // every slot, one 1024-thread workgroup per CU at most (sixteen slots in flight each)
@@ -1483,8 +1527,7 @@ int upload_h2d(bpe_ctx *c, void *dst, const void *src, size_t bytes) {
         return BPE_OK;
     }
     if (!c->h_stage) {
-        if (hipHostMalloc((void **)&c->h_stage, STAGE_PIECE * STAGE_R, hipHostMallocDefault) != hipSuccess) {
-            c->h_stage = nullptr;
+        if (c->h_stage.alloc(STAGE_PIECE * STAGE_R, hipHostMallocDefault) != hipSuccess) {
             (void)hipGetLastError();
             HIPCHK(c, hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, c->stream));  // (no pinned memory to be had: the plain path)
             return BPE_OK;

@@ -17,14 +17,8 @@ extern "C" int bpe_decode_set_vocab(bpe_ctx *c, const uint8_t *vocab_bytes, cons
     c->dec_have_vocab = false;
     c->dec_have_result = false;
     c->dec_meta_valid = false;  // (bpe_token_spans_resident makes the entries' UTF-8 meta anew, on the device)
-    if (nb + 16 > c->cap_dec_blob) {
-        TRY(dev_realloc(c, c->d_dec_blob, (size_t)nb + 16));
-        c->cap_dec_blob = nb + 16;
-    }
-    if ((uint64_t)V + 1 > c->cap_dec_voff) {
-        TRY(dev_realloc(c, c->d_dec_voff, (size_t)V + 1));
-        c->cap_dec_voff = (uint64_t)V + 1;
-    }
+    TRY(grow(c, c->cap_dec_blob, nb + 16, c->d_dec_blob));
+    TRY(grow(c, c->cap_dec_voff, (uint64_t)V + 1, c->d_dec_voff));
     if (nb) HIPCHK(c, hipMemcpyAsync(c->d_dec_blob, vocab_bytes, nb, hipMemcpyHostToDevice, c->stream));
     HIPCHK(c, hipMemcpyAsync(c->d_dec_voff, vocab_offsets, ((size_t)V + 1) * sizeof(uint64_t),
                              hipMemcpyHostToDevice, c->stream));
@@ -52,9 +46,7 @@ extern "C" int bpe_decode_set_sparse(bpe_ctx *c, const int32_t *sparse_ids, int3
     if ((uint64_t)n_sparse > c->cap_dec_sparse) {
         c->dec_V_dense = c->dec_V;  // (nothing half set if the allocation fails)
         c->dec_n_sparse = 0;
-        c->cap_dec_sparse = 0;
-        TRY(dev_realloc(c, c->d_dec_sparse, (size_t)n_sparse));
-        c->cap_dec_sparse = (uint64_t)n_sparse;
+        TRY(grow(c, c->cap_dec_sparse, (uint64_t)n_sparse, c->d_dec_sparse));
     }
     if (n_sparse) {
         HIPCHK(c, hipMemcpyAsync(c->d_dec_sparse, sparse_ids, (size_t)n_sparse * sizeof(int32_t), hipMemcpyHostToDevice,
@@ -99,10 +91,7 @@ extern "C" int bpe_decode_batch(bpe_ctx *c, const int32_t *ids, uint64_t n, uint
         return fail(c, BPE_E_ARG, "invalid token id: %d (position %llu)", ids[hb[0]], hb[0]);
     }
     const uint64_t total = hb[1];
-    if (total + 16 > c->cap_dec_out) {
-        TRY(dev_realloc(c, c->d_dec_out, (size_t)total + 16));
-        c->cap_dec_out = total + 16;
-    }
+    TRY(grow(c, c->cap_dec_out, total + 16, c->d_dec_out));
     TRY(prof_begin(c, BPE_PROF_DECODE, total));
     hipLaunchKernelGGL(k_decode_copy, dim3(grid_for(n, 256, c->num_cus * 8)), dim3(256), 0, c->stream,
                        c->d_dec_ids, n, c->d_dec_voff, c->dec_V, c->d_dec_blob, c->d_dec_off, c->d_dec_out);
@@ -132,15 +121,15 @@ extern "C" int bpe_decode_read(bpe_ctx *c, uint8_t *out, uint64_t cap, const uin
         if (c->dec_n == 0) {  // nothing was decoded: every offset is 0
             for (uint64_t j = 0; j < k; j++) doc_byte_offsets_out[j] = 0;
         } else {
-            DevTmp t_idx, t_dst;
-            HIPCHK(c, t_idx.alloc(k * 8));
-            HIPCHK(c, t_dst.alloc(k * 8));
-            HIPCHK(c, hipMemcpyAsync(t_idx.p, doc_token_offsets, k * 8, hipMemcpyHostToDevice, c->stream));
+            DevPtr<unsigned long long> t_idx, t_dst;
+            TRY(dev_realloc(c, t_idx, k));
+            TRY(dev_realloc(c, t_dst, k));
+            HIPCHK(c, hipMemcpyAsync(t_idx, doc_token_offsets, k * 8, hipMemcpyHostToDevice, c->stream));
             hipLaunchKernelGGL(k_decode_doc_offsets, dim3((unsigned)((k + 255) / 256)), dim3(256), 0, c->stream,
-                               c->d_dec_off, c->dec_n, (unsigned long long)c->dec_total, t_idx.as<unsigned long long>(), k,
-                               t_dst.as<unsigned long long>(), (unsigned long long *)nullptr);
+                               c->d_dec_off, c->dec_n, (unsigned long long)c->dec_total, t_idx, k,
+                               t_dst, (unsigned long long *)nullptr);
             LAUNCHCHK(c, "k_decode_doc_offsets");
-            HIPCHK(c, hipMemcpyAsync(doc_byte_offsets_out, t_dst.p, k * 8, hipMemcpyDeviceToHost, c->stream));
+            HIPCHK(c, hipMemcpyAsync(doc_byte_offsets_out, t_dst, k * 8, hipMemcpyDeviceToHost, c->stream));
             HIPCHK(c, hipStreamSynchronize(c->stream));
         }
     }
@@ -168,13 +157,13 @@ extern "C" int bpe_decode_batch_resident(bpe_ctx *c, const void *d_ids, int32_t 
             using T = decltype(t);
             hipLaunchKernelGGL(k_decode_res_len<T>, dim3(grid_for(n, 256, c->num_cus * 8)), dim3(256), 0, c->stream,
                                (const T *)d_ids, n, c->d_dec_voff, c->dec_V_dense, c->d_dec_sparse, c->dec_n_sparse,
-                               (uint32_t *)c->d_dec_ids, c->d_dec_len, d_bad);
+                               (uint32_t *)c->d_dec_ids.get(), c->d_dec_len, d_bad);
         });
         LAUNCHCHK(c, "k_decode_res_len");
         return BPE_OK;
     };
     auto place = [&](uint64_t total) -> int {
-        uint32_t *d_tidx = (uint32_t *)c->d_dec_ids;
+        uint32_t *d_tidx = (uint32_t *)c->d_dec_ids.get();
         if (c->dec_copy) {
             const uint64_t ntiles = (n + (uint64_t)c->dec_tile - 1) / (uint64_t)c->dec_tile;
             const unsigned grid = (unsigned)std::min<uint64_t>(ntiles, (uint64_t)c->num_cus * 64);

@@ -20,12 +20,10 @@ extern "C" int bpe_dp_begin(bpe_ctx *c, int32_t num_merges, int32_t rank, int32_
     HIPCHK(c, hipMemsetAsync(c->d_dbits, 0, DBITS_WORDS * sizeof(uint32_t), c->stream));
     TRY(ensure_rec(c, std::max(num_merges, 1)));
     memset(c->h_rec, 0, sizeof(IterRec) * (size_t)std::max(num_merges, 1));
-    if (c->d_dp_folded) (void)hipFree(c->d_dp_folded);
-    c->d_dp_folded = nullptr;
-    HIPCHK(c, hipMalloc((void **)&c->d_dp_folded, ((size_t)c->vcap * 4 + 64) * sizeof(uint32_t)));
+    TRY(dev_realloc(c, c->d_dp_folded, (size_t)c->vcap * 4 + 64));
     HIPCHK(c, hipMemsetAsync(c->d_dp_folded, 0, ((size_t)c->vcap * 4 + 64) * sizeof(uint32_t), c->stream));
-    if (!c->d_dp_table) HIPCHK(c, hipMalloc((void **)&c->d_dp_table, 2 * 256 * 256 * sizeof(uint32_t)));
-    if (!c->d_dp_key) HIPCHK(c, hipMalloc((void **)&c->d_dp_key, 3 * sizeof(long long)));
+    TRY(dev_once(c, c->d_dp_table, 2 * 256 * 256));
+    TRY(dev_once(c, c->d_dp_key, 3));
     HIPCHK(c, hipMemsetAsync(c->d_mat, 0, (size_t)c->vcap * c->vcap * sizeof(uint32_t), c->stream));
     const bool fused_load = load_count_fusable(c);
     TRY(start_from_bytes(c, fused_load));

@@ -8,10 +8,7 @@ namespace {
 inline uint64_t mix_key(uint64_t key) { return (key * 0x9E3779B97F4A7C15ull) >> 40; }
 
 int upload_offsets(bpe_ctx *c, const uint64_t *chunk_offsets, uint64_t n_chunks) {
-    if (n_chunks > c->cap_offsets) {
-        TRY(dev_realloc(c, c->d_offsets, (size_t)n_chunks));
-        c->cap_offsets = n_chunks;
-    }
+    TRY(grow(c, c->cap_offsets, n_chunks, c->d_offsets));
     if (n_chunks) TRY(upload_h2d(c, c->d_offsets, chunk_offsets, n_chunks * sizeof(uint64_t)));
     return BPE_OK;
 }
@@ -98,10 +95,8 @@ int encode_batch_impl(bpe_ctx *c, const int32_t *merges, const int32_t *merge_id
             const int saved_mode = c->mode;
             c->mode = 1;
             int rc = bpe_load_bytes(c, bytes, n, nullptr, 0);
-            if (rc == BPE_OK && (uint64_t)M > c->cap_forced) {
-                rc = dev_realloc(c, c->d_forced, (size_t)2 * (size_t)M);
-                if (rc == BPE_OK) c->cap_forced = (uint64_t)M;
-            }
+            if (rc == BPE_OK)  // (cap_forced counts merges: two ids each)
+                rc = grow_group(c->cap_forced, (uint64_t)M, [&]() -> int { return dev_realloc(c, c->d_forced, (size_t)2 * (size_t)M); });
             if (rc == BPE_OK && hipMemcpyAsync(c->d_forced, merges, (size_t)2 * (size_t)M * sizeof(int32_t), hipMemcpyHostToDevice, c->stream) != hipSuccess)
                 rc = fail(c, BPE_E_HIP, "upload of the merge list failed");
             int32_t done = 0;
@@ -115,7 +110,7 @@ int encode_batch_impl(bpe_ctx *c, const int32_t *merges, const int32_t *merge_id
             if (rc != BPE_OK) return rc;
             const uint64_t total = c->n;
             if (ids_out && total) {
-                int32_t *tmp = (int32_t *)c->d_ids[c->par ^ 1];
+                int32_t *tmp = (int32_t *)c->d_ids[c->par ^ 1].get();
                 hipLaunchKernelGGL(k_strip_flags, dim3(grid_for(total, 256, c->num_cus * 8)), dim3(256), 0, c->stream, c->d_ids[c->par], tmp, total);
                 LAUNCHCHK(c, "k_strip_flags");
                 TRY(download_d2h(c, ids_out, tmp, total * sizeof(int32_t)));
@@ -152,50 +147,41 @@ int encode_batch_impl(bpe_ctx *c, const int32_t *merges, const int32_t *merge_id
         hk[h] = key;
         hv[h] = (uint32_t)r;  // a repeated pair keeps its last entry, like a dict
     }
-    if (hs > c->cap_ht) {
+    TRY(grow_group(c->cap_ht, hs, [&]() -> int {
         TRY(dev_realloc(c, c->d_ht_keys, (size_t)hs));
-        TRY(dev_realloc(c, c->d_ht_vals, (size_t)hs));
-        c->cap_ht = hs;
-    }
+        return dev_realloc(c, c->d_ht_vals, (size_t)hs);
+    }));
     HIPCHK(c, hipMemcpyAsync(c->d_ht_keys, hk.data(), hs * 8, hipMemcpyHostToDevice, c->stream));
     HIPCHK(c, hipMemcpyAsync(c->d_ht_vals, hv.data(), hs * 4, hipMemcpyHostToDevice, c->stream));
     const int32_t *d_mids = nullptr;
     if (merge_ids && M) {
-        if ((uint64_t)M > c->cap_merge_ids) {
-            TRY(dev_realloc(c, c->d_merge_ids, (size_t)M));
-            c->cap_merge_ids = (uint64_t)M;
-        }
+        TRY(grow(c, c->cap_merge_ids, (uint64_t)M, c->d_merge_ids));
         HIPCHK(c, hipMemcpyAsync(c->d_merge_ids, merge_ids, (size_t)M * 4, hipMemcpyHostToDevice, c->stream));
         d_mids = c->d_merge_ids;
     }
     // 2. input
-    if (n + 16 > c->cap_bytes) {
-        TRY(dev_realloc(c, c->d_bytes, (size_t)n + 16));
-        c->cap_bytes = n + 16;
-    }
+    TRY(grow(c, c->cap_bytes, n + 16, c->d_bytes));
     // (the bytes are copied either way: the kernels read up to 16 bytes past the end of the ctx's padded buffer)
     if (resident) HIPCHK(c, hipMemcpyAsync(c->d_bytes, bytes, n, hipMemcpyDeviceToDevice, c->stream));
     else TRY(upload_h2d(c, c->d_bytes, bytes, n));  // (pinned staging ring, several host threads: api_ctx.hip)
     if (!resident) TRY(upload_offsets(c, chunk_offsets, n_chunks));
     const uint64_t *d_offs = resident ? chunk_offsets : c->d_offsets;
     // 3. scratch
-    if (n > c->cap_enc_n) {
+    TRY(grow_group(c->cap_enc_n, n, [&]() -> int {
         TRY(dev_realloc(c, c->d_enc_tmp, (size_t)n));
         TRY(dev_realloc(c, c->d_enc_out, (size_t)n));
         TRY(dev_realloc(c, c->d_enc_long, (size_t)(n / (ENC_LMAX + 1) + 2)));
-        TRY(dev_realloc(c, c->d_enc_huge, (size_t)(n / (ENC_LONG_MAX + 1) + 2)));
-        c->cap_enc_n = n;
-    }
+        return dev_realloc(c, c->d_enc_huge, (size_t)(n / (ENC_LONG_MAX + 1) + 2));
+    }));
     const uint64_t nb = scan_tiles(n_chunks);
-    if (n_chunks > c->cap_enc_chunks) {
+    TRY(grow_group(c->cap_enc_chunks, n_chunks, [&]() -> int {
         TRY(dev_realloc(c, c->d_enc_len, (size_t)n_chunks));
         TRY(dev_realloc(c, c->d_enc_off, (size_t)n_chunks + 1));
         TRY(dev_realloc(c, c->d_enc_bsum, (size_t)nb * (SCAN_TILE / ENC_PLACE_TILE) + 2));  // (also the chained pass's descriptors)
         TRY(dev_realloc(c, c->d_enc_rep, (size_t)n_chunks));
         TRY(dev_realloc(c, c->d_enc_mid, (size_t)((n_chunks + ENC_THREADS - 1) / ENC_THREADS) * ENC_THREADS));
-        TRY(dev_realloc(c, c->d_enc_midn, (size_t)((n_chunks + ENC_THREADS - 1) / ENC_THREADS)));
-        c->cap_enc_chunks = n_chunks;
-    }
+        return dev_realloc(c, c->d_enc_midn, (size_t)((n_chunks + ENC_THREADS - 1) / ENC_THREADS));
+    }));
     int32_t *d_out = resident ? ids_out : c->d_enc_out;
     unsigned long long *d_ooff = resident ? (unsigned long long *)out_offsets : c->d_enc_off;
     // the chunk cache (k_encode.hip): a slot per four chunks, 2^12 .. 2^22 slots of 32 bytes (the distinct
@@ -204,10 +190,7 @@ int encode_batch_impl(bpe_ctx *c, const int32_t *merges, const int32_t *merge_id
     uint64_t tslots = 1ull << 12;
     while (tslots < n_chunks / 4 && tslots < (1ull << 22)) tslots <<= 1;
     if (cache) {
-        if (tslots > c->cap_enc_tab) {
-            TRY(dev_realloc(c, c->d_enc_tab, (size_t)tslots));
-            c->cap_enc_tab = tslots;
-        }
+        TRY(grow(c, c->cap_enc_tab, tslots, c->d_enc_tab));
         // (key 0 = empty; rep all ones: the atomicMin of the hashed chunks starts from there)
         HIPCHK(c, hipMemsetAsync(c->d_enc_tab, 0, tslots * sizeof(EncEntry), c->stream));
         hipLaunchKernelGGL(k_enc_tab_init, dim3((unsigned)((tslots + 255) / 256)), dim3(256), 0, c->stream, c->d_enc_tab,
@@ -274,14 +257,14 @@ int encode_batch_impl(bpe_ctx *c, const int32_t *merges, const int32_t *merge_id
         unsigned long long tot = 0;
         std::vector<unsigned long long> range(2 * n_long);
         if (resident) {  // (the caller's offsets live on the device: the chunks' byte ranges in one kernel and one copy)
-            DevTmp t_list, t_range;
-            HIPCHK(c, t_list.alloc(n_long * 8));
-            HIPCHK(c, t_range.alloc(2 * n_long * 8));
-            HIPCHK(c, hipMemcpyAsync(t_list.as<unsigned long long>(), ids_l.data(), n_long * 8, hipMemcpyHostToDevice, c->stream));
+            DevPtr<unsigned long long> t_list, t_range;
+            TRY(dev_realloc(c, t_list, n_long));
+            TRY(dev_realloc(c, t_range, 2 * n_long));
+            HIPCHK(c, hipMemcpyAsync(t_list, ids_l.data(), n_long * 8, hipMemcpyHostToDevice, c->stream));
             hipLaunchKernelGGL(k_long_ranges, dim3((unsigned)((n_long + 255) / 256)), dim3(256), 0, c->stream, d_offs, n_chunks, n,
-                               t_list.as<unsigned long long>(), (uint64_t)n_long, t_range.as<unsigned long long>());
+                               t_list, (uint64_t)n_long, t_range);
             LAUNCHCHK(c, "k_long_ranges");
-            HIPCHK(c, hipMemcpyAsync(range.data(), t_range.as<unsigned long long>(), 2 * n_long * 8, hipMemcpyDeviceToHost, c->stream));
+            HIPCHK(c, hipMemcpyAsync(range.data(), t_range, 2 * n_long * 8, hipMemcpyDeviceToHost, c->stream));
             HIPCHK(c, hipStreamSynchronize(c->stream));
         } else {
             for (uint64_t k = 0; k < n_long; k++) {
@@ -299,13 +282,11 @@ int encode_batch_impl(bpe_ctx *c, const int32_t *merges, const int32_t *merge_id
         dst[n_long] = tot;
         TRY(ensure_table(c, 256));
         TRY(ensure_ids(c, tot));
-        DevTmp t_src, t_dst, t_cid, t_starts;
-        HIPCHK(c, t_src.alloc(n_long * 8));
-        HIPCHK(c, t_dst.alloc((n_long + 1) * 8));
-        HIPCHK(c, t_cid.alloc(n_long * 8));
-        HIPCHK(c, t_starts.alloc((n_long + 1) * 8));
-        unsigned long long *d_src = t_src.as<unsigned long long>(), *d_dst = t_dst.as<unsigned long long>(),
-                           *d_cid = t_cid.as<unsigned long long>(), *d_starts = t_starts.as<unsigned long long>();
+        DevPtr<unsigned long long> d_src, d_dst, d_cid, d_starts;
+        TRY(dev_realloc(c, d_src, n_long));
+        TRY(dev_realloc(c, d_dst, n_long + 1));
+        TRY(dev_realloc(c, d_cid, n_long));
+        TRY(dev_realloc(c, d_starts, n_long + 1));
         HIPCHK(c, hipMemcpyAsync(d_src, src.data(), n_long * 8, hipMemcpyHostToDevice, c->stream));
         HIPCHK(c, hipMemcpyAsync(d_dst, dst.data(), (n_long + 1) * 8, hipMemcpyHostToDevice, c->stream));
         HIPCHK(c, hipMemcpyAsync(d_cid, ids_l.data(), n_long * 8, hipMemcpyHostToDevice, c->stream));

@@ -17,11 +17,7 @@ extern "C" int bpe_project_set_merges(bpe_ctx *c, const int32_t *merges, int32_t
     HIPCHK(c, hipSetDevice(c->device));
     c->proj_M = -1;  // (nothing half set if a step below fails)
     c->proj_vs = -1;
-    if ((uint64_t)n_pass > c->cap_proj_pass) {
-        c->cap_proj_pass = 0;
-        TRY(dev_realloc(c, c->d_proj_pass, (size_t)n_pass));
-        c->cap_proj_pass = (uint64_t)n_pass;
-    }
+    TRY(grow(c, c->cap_proj_pass, (uint64_t)n_pass, c->d_proj_pass));
     if (n_pass) {
         HIPCHK(c, hipMemcpyAsync(c->d_proj_pass, pass_ids, (size_t)n_pass * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
         HIPCHK(c, hipStreamSynchronize(c->stream));  // caller may free its buffer on return
@@ -102,16 +98,8 @@ extern "C" int bpe_project_resident(bpe_ctx *c, const void *d_ids, int32_t id_wi
     HIPCHK(c, hipSetDevice(c->device));
     if (fresh) {  // once per vocab_size: a second call at the same size builds and uploads nothing
         c->proj_vs = -1;
-        if (tab.size() > c->cap_proj_tab) {
-            c->cap_proj_tab = 0;
-            TRY(dev_realloc(c, c->d_proj_tab, tab.size()));
-            c->cap_proj_tab = tab.size();
-        }
-        if (toff.size() > c->cap_proj_toff) {
-            c->cap_proj_toff = 0;
-            TRY(dev_realloc(c, c->d_proj_toff, toff.size()));
-            c->cap_proj_toff = toff.size();
-        }
+        TRY(grow(c, c->cap_proj_tab, tab.size(), c->d_proj_tab));
+        TRY(grow(c, c->cap_proj_toff, toff.size(), c->d_proj_toff));
         if (!tab.empty())
             HIPCHK(c, hipMemcpyAsync(c->d_proj_tab, tab.data(), tab.size() * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
         HIPCHK(c, hipMemcpyAsync(c->d_proj_toff, toff.data(), toff.size() * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));

@@ -117,12 +117,9 @@ int dp_train_loop(bpe_ctx *c, int32_t num_merges, const DpComm &comm, int32_t *p
     c->dp_comm = &comm;
     TRY(bpe_dp_begin(c, num_merges, comm.rank, comm.nranks));
     TRY(ensure_srec(c));
-    if (!c->d_dp_ckey) HIPCHK(c, hipMalloc((void **)&c->d_dp_ckey, DP_KEY_WORDS * sizeof(long long)));
+    TRY(dev_once(c, c->d_dp_ckey, DP_KEY_WORDS));
     const uint64_t cfold_words = (uint64_t)2 * DP_KCAP_MAX * c->vcap + 64;
-    if (cfold_words > c->cap_dp_cfold) {
-        TRY(dev_realloc(c, c->d_dp_cfold, (size_t)cfold_words));
-        c->cap_dp_cfold = cfold_words;
-    }
+    TRY(grow(c, c->cap_dp_cfold, cfold_words, c->d_dp_cfold));
     HIPCHK(c, hipMemsetAsync(c->d_dp_cfold, 0, cfold_words * sizeof(uint32_t), c->stream));
     HIPCHK(c, hipMemsetAsync(c->d_dp_ckey, 0, DP_KEY_WORDS * sizeof(long long), c->stream));
     TRY(dp_allreduce(c, c->d_dp_table, 2 * 256 * 256, BPE_DT_INT32, BPE_OP_SUM));  // (16-bit limbs: bpe_dp_begin)
@@ -349,9 +346,8 @@ int dp_train_loop(bpe_ctx *c, int32_t num_merges, const DpComm &comm, int32_t *p
     c->dp_active = false;
     // global lengths: one SUM over the per-shard lengths (every rank, also after a failure: `done` is the same everywhere)
     if (num_merges > 0) {
-        DevTmp t_l;
-        HIPCHK(c, t_l.alloc((size_t)num_merges * 8));
-        long long *d_l = t_l.as<long long>();
+        DevPtr<long long> d_l;
+        TRY(dev_realloc(c, d_l, (size_t)num_merges));
         HIPCHK(c, hipMemcpyAsync(d_l, lens.data(), (size_t)num_merges * 8, hipMemcpyHostToDevice, c->stream));
         TRY(dp_allreduce(c, d_l, (uint64_t)num_merges, BPE_DT_INT64, BPE_OP_SUM));
         HIPCHK(c, hipMemcpyAsync(lens.data(), d_l, (size_t)num_merges * 8, hipMemcpyDeviceToHost, c->stream));

@@ -26,13 +26,12 @@ int scan_lengths(bpe_ctx *c, const uint32_t *len, uint64_t n, unsigned long long
 
 // the decode scratch (ids / resolved indices, lengths, their scan and its block sums) holds n tokens
 int ensure_dec_scratch(bpe_ctx *c, uint64_t n) {
-    if (n <= c->cap_dec_n) return BPE_OK;
-    TRY(dev_realloc(c, c->d_dec_ids, (size_t)n));
-    TRY(dev_realloc(c, c->d_dec_len, (size_t)n));
-    TRY(dev_realloc(c, c->d_dec_off, (size_t)n + 1));
-    TRY(dev_realloc(c, c->d_dec_bsum, (size_t)scan_tiles(n) + 1));
-    c->cap_dec_n = n;
-    return BPE_OK;
+    return grow_group(c->cap_dec_n, n, [&]() -> int {
+        TRY(dev_realloc(c, c->d_dec_ids, (size_t)n));
+        TRY(dev_realloc(c, c->d_dec_len, (size_t)n));
+        TRY(dev_realloc(c, c->d_dec_off, (size_t)n + 1));
+        return dev_realloc(c, c->d_dec_bsum, (size_t)scan_tiles(n) + 1);
+    });
 }
 
 // what a user of resident_two_pass says besides its two launches

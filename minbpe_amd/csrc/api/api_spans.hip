@@ -8,11 +8,7 @@
 // first spans call after it, never on the host
 static int spans_meta(bpe_ctx *c) {
     if (c->dec_meta_valid) return BPE_OK;
-    if ((uint64_t)c->dec_V > c->cap_dec_meta) {
-        c->cap_dec_meta = 0;
-        TRY(dev_realloc(c, c->d_dec_meta, (size_t)c->dec_V));
-        c->cap_dec_meta = c->dec_V;
-    }
+    TRY(grow(c, c->cap_dec_meta, c->dec_V, c->d_dec_meta));
     if (c->dec_V) {
         unsigned long long *d_limit = &c->d_scratch->count;
         HIPCHK(c, hipMemsetAsync(d_limit, 0, sizeof(unsigned long long), c->stream));
@@ -52,21 +48,16 @@ extern "C" int bpe_token_spans_resident(bpe_ctx *c, const void *d_ids, int32_t i
     const bool docs = d_doc_offsets != nullptr;
     const uint64_t nb = scan_tiles(n);
     TRY(ensure_dec_scratch(c, n));
-    if (n > c->cap_spn_n) {
-        c->cap_spn_n = 0;
+    TRY(grow_group(c->cap_spn_n, n, [&]() -> int {
         TRY(dev_realloc(c, c->d_spn_off, (size_t)n + 1));
-        TRY(dev_realloc(c, c->d_spn_bsum, (size_t)nb + 1));
-        c->cap_spn_n = n;
-    }
-    if (docs && n_docs + 1 > c->cap_spn_docs) {
-        c->cap_spn_docs = 0;
-        TRY(dev_realloc(c, c->d_spn_base, 2 * ((size_t)n_docs + 1)));
-        c->cap_spn_docs = n_docs + 1;
-    }
+        return dev_realloc(c, c->d_spn_bsum, (size_t)nb + 1);
+    }));
+    if (docs)
+        TRY(grow_group(c->cap_spn_docs, n_docs + 1, [&]() -> int { return dev_realloc(c, c->d_spn_base, 2 * ((size_t)n_docs + 1)); }));
     // {first bad position, total bytes, total leads, first bad offset entry, off[0], off[n_docs]}
     auto *w = &c->d_scratch->spans;
     unsigned long long *d_bad = &w->bad, *d_totals = w->totals, *d_docbad = &w->docbad, *d_ends = w->ends;
-    uint32_t *d_len = c->d_dec_len, *d_lw = (uint32_t *)c->d_dec_ids;
+    uint32_t *d_len = c->d_dec_len, *d_lw = (uint32_t *)c->d_dec_ids.get();
     HIPCHK(c, hipMemsetAsync(d_bad, 0xFF, 4 * sizeof(unsigned long long), c->stream));  // bad, totals, docbad
     if (docs) {
         hipLaunchKernelGGL(k_rows_check, dim3(grid_for(n_docs + 1, 256, c->num_cus * 8)), dim3(256), 0, c->stream,

@@ -24,8 +24,7 @@ int bpe_train(bpe_ctx *c, int32_t num_merges, int32_t *pairs_out, uint64_t *coun
     TRY(ensure_srec(c));
     const bool delta = (c->mode == 1);
     // one event after every unit of work enqueued (an iteration, or a chain step of 1..CH_KMAX merges)
-    EventList ev_list;  // destroyed on every exit path
-    std::vector<hipEvent_t> &evs = ev_list.v;
+    EventList evs;  // destroyed on every exit path
     struct EvSpan {
         int ev, first, k;
     };
@@ -72,7 +71,7 @@ int bpe_train(bpe_ctx *c, int32_t num_merges, int32_t *pairs_out, uint64_t *coun
     static const char *stamp_path = getenv("BPE_STEP_STAMPS");
     const size_t stamp_bytes = (size_t)STEP_STAMP_RING * (3 * 16 + 256 * 2) * sizeof(unsigned long long);
     if (stamp_path) {
-        if (!c->d_step_stamps) HIPCHK(c, hipMalloc((void **)&c->d_step_stamps, stamp_bytes));
+        TRY(dev_once(c, c->d_step_stamps, stamp_bytes / sizeof(unsigned long long)));
         HIPCHK(c, hipMemsetAsync(c->d_step_stamps, 0, stamp_bytes, c->stream));
     }
     if (c->d_step_bar) {  // (a launch that a device status cut short in an earlier call may have left the count short)

@@ -44,6 +44,7 @@ struct ProfEv {
 
 // the parts, in order (one translation unit: the kernels above are launched from all of them)
 #include "api/api_ctx.hip"
+#include "api/api_options.hip"
 #include "api/api_resident.hip"
 #include "api/api_basic.hip"
 #include "api/api_train.hip"
