@@ -76,7 +76,11 @@ int bpe_set_stream(bpe_ctx *ctx, void *hip_stream);
  *   memory instead, and 0 makes every tile do so -- the cross-check form);
  *   bpe_token_spans_resident's emit kernel: "spans_stage" (1024, 0..4096: the same for its tiles of 1024 tokens);
  *   bpe_project_resident's placement kernel: "proj_tile" (256: tokens per workgroup tile, 64..16384, a multiple of
- *   64), "proj_window" (2048: ids of its LDS window, 64..8192, a multiple of 4). */
+ *   64), "proj_window" (2048: ids of its LDS window, 64..8192, a multiple of 4);
+ *   bpe_count_resident's counting kernel: "count_lds_bins" (32768: the first bins, counted in a workgroup's LDS,
+ *   256..32768, a multiple of 256), "count_flush" (2^31: ids a workgroup counts between flushes of that table,
+ *   64..2^31), "count_combine" (0: one add per id | 1 equal ids among the 16 bytes a lane loads are one add; measured
+ *   no faster). */
 int bpe_set_option(bpe_ctx *ctx, const char *name, int64_t value);
 
 /* ---- input ----------------------------------------------------------------- */
@@ -390,6 +394,43 @@ int bpe_project_resident(bpe_ctx *ctx, const void *d_ids, int32_t id_width, uint
                          const uint64_t *d_doc_token_offsets, uint64_t k,
                          void *d_out, uint64_t out_cap, uint64_t *d_doc_out_offsets,
                          uint64_t *n_out, uint64_t *bad_index);
+
+/* ---- token counts: id histogram and the compression curve ------------- */
+/* How often each id occurs in ids that live in HBM, and from that histogram alone -- no second look at the ids -- the
+ * histogram and the token count at every smaller vocabulary.
+ *   bins             B = 256 + M + P of them, M and the P pass ids being those of bpe_project_set_merges: bin t for
+ *                    0 <= t < 256 + M, bin 256 + M + j for the j-th pass id in ascending order
+ *   bpe_count_resident   d_counts[i] = occurrences of bin i's id among the n ids of d_ids (DEVICE buffers, the caller's)
+ *   d_ids, id_width  n ids of 4 (int32) or 8 (int64) bytes at any address aligned to id_width, read in place; a 64-bit id
+ *                    is compared at its full width
+ *   d_counts, n_bins B uint64; n_bins must equal B -- the caller's statement of the layout --, else BPE_E_ARG
+ *   accumulate       0: d_counts[i] = the count; otherwise d_counts[i] += the count (a corpus larger than HBM, batch by
+ *                    batch)
+ *   *bad_index       first position whose id has no bin (~0 if none): BPE_E_ARG, and nothing is written to d_counts, in
+ *                    either mode
+ * Nothing outside d_counts[0, B) is ever written.  n = 0 is BPE_OK: zeros, or the array as it is when accumulating.
+ * BPE_E_STATE before bpe_project_set_merges; BPE_E_ARG: id_width not 4 or 8, d_ids = NULL with n > 0, d_counts = NULL, a
+ * misaligned pointer.  The call counts into a scratch of the ctx's own -- the first "count_lds_bins" bins (32768;
+ * 256..32768, a multiple of 256) in LDS tables private to a workgroup, flushed at the end and every "count_flush" ids of
+ * a workgroup (2^31; 64..2^31), the rest by 64-bit adds to memory; "count_combine" (0): 1 = equal ids among the 16 bytes
+ * a lane loads are one add instead of one add per id -- and commits it to d_counts once the host has read
+ * back that no id was bad.  Runs on the ctx's stream and synchronises it before returning; keeps no pointer of the
+ * caller's; one counter crosses PCIe.  The decode scratch, a bpe_decode_batch result not yet read, the decode table and
+ * the projection table are not touched.
+ *   bpe_count_fold   host only, no ctx.  counts: a histogram in the layout above (n_bins >= 256 + M words; those from
+ *                    256 + M on are pass bins).  Undoing merge t -> (a, b) adds counts[t] tokens and moves counts[t]
+ *                    into a's and b's bins; t walks from 255 + M down
+ *   folded           n_bins words or NULL: the histogram at vocab_size -- bins [vocab_size, 256 + M) zero, pass bins
+ *                    unchanged
+ *   curve            M + 1 words or NULL: curve[k] = tokens at 256 + k entries; curve[M] = the sum of all bins,
+ *                    curve[k] = curve[k + 1] + (the histogram at 256 + k + 1 entries)[256 + k]
+ * BPE_E_ARG: a merge list of another shape than bpe_project_set_merges takes, vocab_size outside [256, 256 + M],
+ * n_bins < 256 + M, counts = NULL.  Every add is checked: a sum of 2^64 or more is BPE_E_LIMIT, and the outputs are then
+ * undefined. */
+int bpe_count_resident(bpe_ctx *ctx, const void *d_ids, int32_t id_width, uint64_t n,
+                       uint64_t *d_counts, uint64_t n_bins, int32_t accumulate, uint64_t *bad_index);
+int bpe_count_fold(const int32_t *merges, int32_t M, const uint64_t *counts, uint64_t n_bins,
+                   int32_t vocab_size, uint64_t *folded, uint64_t *curve);
 
 /* ---- measurement ------------------------------------------------------------ */
 #define BPE_PROF_WIDEN 0

@@ -105,6 +105,8 @@ _SIGS = {
     "bpe_project_set_merges": (C.c_int, [_p, _p, _i32, _p, _i32]),
     "bpe_project_resident": (C.c_int, [_p, _p, _i32, _u64, _i32, _p, _u64, _p, _u64, _p, C.POINTER(_u64),
                                        C.POINTER(_u64)]),
+    "bpe_count_resident": (C.c_int, [_p, _p, _i32, _u64, _p, _u64, _i32, C.POINTER(_u64)]),
+    "bpe_count_fold": (C.c_int, [_p, _i32, _p, _u64, _i32, _p, _p]),
     "bpe_prof_reset": (C.c_int, [_p]),
     "bpe_prof_read": (C.c_int, [_p, _p, _p, _p]),
     "bpe_encode_uses_16bit": (C.c_int, [_p, C.c_int32]),
@@ -220,6 +222,38 @@ def dedup_chunks(data: bytes, offsets, threads: int = 0):
     if rc != BPE_OK:
         raise RuntimeError(f"bpe_dedup_chunks failed: {rc}")
     return out[:nb.value].tobytes(), ooff[:nc.value].copy(), wexp[:nc.value].copy(), int(nd.value)
+
+
+def count_fold(pairs, counts, vocab_size=None, want_curve=True):
+    """bpe_count_fold (host only): pairs [M, 2] int32 in merge order, counts a histogram of at least 256 + M bins in the
+    layout of Engine.count_resident (non-negative integers).  Returns (folded, curve): the histogram at vocab_size as
+    uint64 [len(counts)] (None without a vocab_size), and the tokens at every size 256 .. 256 + M as int64 [M + 1] (None
+    with want_curve=False).  ValueError for a list of another shape than training makes, a vocab_size outside
+    [256, 256 + M], too few bins or a negative count; OverflowError when a sum does not fit (the curve: int64)."""
+    pairs = np.ascontiguousarray(pairs, dtype=np.int32).reshape(-1, 2)
+    arr = np.asarray(counts)
+    if arr.ndim != 1 or (arr.size and arr.dtype.kind not in "iu"):
+        raise TypeError("counts must be a 1-D array of integers")
+    if arr.dtype.kind == "i" and arr.size and int(arr.min()) < 0:
+        raise ValueError("counts must not be negative")
+    cnt = np.ascontiguousarray(arr, dtype=np.uint64)
+    M = len(pairs)
+    folded = None if vocab_size is None else np.empty(len(cnt), np.uint64)
+    curve = np.empty(M + 1, np.uint64) if want_curve else None
+    rc = _lib.bpe_count_fold(_ptr(pairs) if M else None, M, _ptr(cnt) if len(cnt) else None, len(cnt),
+                             256 + M if vocab_size is None else int(vocab_size), _ptr(folded), _ptr(curve))
+    if rc == BPE_E_LIMIT:
+        raise OverflowError("the folded counts pass 2^64")
+    if rc == BPE_E_ARG:
+        raise ValueError("bpe_count_fold: a merge list that does not have the shape training makes, a vocab_size outside "
+                         "[256, 256 + M], or fewer than 256 + M bins")
+    if rc != BPE_OK:
+        raise RuntimeError(f"bpe_count_fold failed: {rc}")
+    if curve is not None:
+        if int(curve[0]) >= 2**63:  # (the curve descends with k: its first entry is the largest)
+            raise OverflowError("the token counts pass 2^63")
+        curve = curve.astype(np.int64)
+    return folded, curve
 
 
 class InvalidToken(Exception):
@@ -650,6 +684,19 @@ class Engine:
             raise OutputTooSmall(int(no.value), (_lib.bpe_last_error(self._h) or b"").decode())
         self._check(rc)
         return int(no.value)
+
+    # -- token counts ------------------------------------------------------------------
+    def count_resident(self, d_ids: int, id_width: int, n: int, d_counts: int, n_bins: int, accumulate: bool = False):
+        """bpe_count_resident: d_ids (n ids of id_width = 4 or 8 bytes) and d_counts (n_bins uint64) are device addresses
+        (e.g. torch tensor.data_ptr()); the bins are those of the list given to project_set_merges, n_bins = 256 + M +
+        the number of pass ids.  accumulate: add to what d_counts holds.  An id that has no bin raises
+        InvalidToken(position), and d_counts is then unchanged."""
+        bad = _u64(0)
+        rc = _lib.bpe_count_resident(self._h, C.c_void_p(d_ids), id_width, n, C.c_void_p(d_counts), n_bins,
+                                     1 if accumulate else 0, C.byref(bad))
+        if rc == BPE_E_ARG and bad.value != 0xFFFFFFFFFFFFFFFF:
+            raise InvalidToken(int(bad.value))
+        self._check(rc)
 
     # -- measurement ----------------------------------------------------------------
     def prof_reset(self):

@@ -53,6 +53,10 @@ int bpe_create(int device_id, bpe_ctx **out) {
     if ((e = hipFuncSetAttribute((const void *)bpe::bpe_g4::k_index_build, hipFuncAttributeMaxDynamicSharedMemorySize,
                                  bpe::bpe_g4::IDX_H * 4)) != hipSuccess)
         return bail("hipFuncSetAttribute(dynamic LDS)", e);
+    for (const void *fn : {(const void *)k_count<int32_t, true>, (const void *)k_count<int32_t, false>,
+                           (const void *)k_count<int64_t, true>, (const void *)k_count<int64_t, false>})
+        if ((e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, COUNT_LDS_BINS_MAX * 4)) != hipSuccess)
+            return bail("hipFuncSetAttribute(dynamic LDS)", e);
     if (dev_once(c, c->d_st, 1) != BPE_OK || dev_once(c, c->d_scratch, 1) != BPE_OK) {
         g_create_err = c->err;
         ctx_free(c);

