@@ -80,7 +80,10 @@ int bpe_set_stream(bpe_ctx *ctx, void *hip_stream);
  *   bpe_count_resident's counting kernel: "count_lds_bins" (32768: the first bins, counted in a workgroup's LDS,
  *   256..32768, a multiple of 256), "count_flush" (2^31: ids a workgroup counts between flushes of that table,
  *   64..2^31), "count_combine" (0: one add per id | 1 equal ids among the 16 bytes a lane loads are one add; measured
- *   no faster). */
+ *   no faster);
+ *   bpe_select_docs_resident's placement kernel: "sel_tile" (4096: output elements per workgroup tile, 64..65536, a
+ *   multiple of 4), "sel_stage" (1024: output starts a tile stages in LDS, 0..4096; a tile that holds more searches
+ *   global memory instead, and 0 makes every tile do so -- the cross-check form). */
 int bpe_set_option(bpe_ctx *ctx, const char *name, int64_t value);
 
 /* ---- input ----------------------------------------------------------------- */
@@ -431,6 +434,48 @@ int bpe_count_resident(bpe_ctx *ctx, const void *d_ids, int32_t id_width, uint64
                        uint64_t *d_counts, uint64_t n_bins, int32_t accumulate, uint64_t *bad_index);
 int bpe_count_fold(const int32_t *merges, int32_t M, const uint64_t *counts, uint64_t n_bins,
                    int32_t vocab_size, uint64_t *folded, uint64_t *curve);
+
+/* ---- document selection: gather, filter and shuffle ids in HBM -------- */
+/* Which documents of an id stream that lives in HBM go on, and in what order: a shuffle, a filter or a sample in front
+ * of rows, decode, spans, projection and counts.  Every large buffer is ON THE DEVICE and owned by the caller.
+ *   off              the n_docs + 1 entries of d_doc_offsets; len(d) = off[d + 1] - off[d]
+ *   selection j      d = index[j];  l_j = len(d) if max_len == 0, otherwise min(len(d), max_len);
+ *                    s_j = off[d], or off[d + 1] - l_j with BPE_SELECT_TAIL
+ *   out              ids[s_0 : s_0 + l_0] | ids[s_1 : s_1 + l_1] | ...
+ *   out_offsets[j]   l_0 + ... + l_{j-1}; out_offsets[m] is the total
+ * index may repeat documents, name them in any order and leave any out; m = 0 gives an empty output with
+ * out_offsets = [0].
+ *   d_ids, id_width  n ids of 4 (int32) or 8 (int64) bytes, read in place, never written
+ *   d_doc_offsets    validated on the device exactly as in bpe_rows_resident: ascending, none beyond n.  The first bad
+ *                    entry goes to *bad_doc (~0 if none) and the call fails with BPE_E_ARG.  Ids before off[0] or at or
+ *                    after off[n_docs] belong to no document and can never reach the output
+ *   d_index, m       m int64 document numbers, each in [0, n_docs), compared at its full 64 bits (a negative one does not
+ *                    wrap).  The lowest offending j goes to *bad_sel (~0 if none) and the call fails with BPE_E_ARG.
+ *                    Offsets are checked first.  On either failure nothing is written to d_out or d_out_offsets
+ *   max_len, flags   max_len = 0: whole documents; otherwise at most max_len ids of each, its head, or its tail with
+ *                    BPE_SELECT_TAIL
+ *   d_out, out_cap   receives the ids, of the input's width; NULL / 0 = only count.  Must not overlap d_ids: the
+ *                    caller's contract.  out_cap < total fails with BPE_E_CAP and leaves d_out untouched
+ *   d_out_offsets    m + 1 words, never NULL; written by a count-only call and on BPE_E_CAP too
+ *   *n_out           the total, set as soon as it is known, also on BPE_E_CAP
+ * Never writes d_out[out_cap] or beyond, nor anything outside d_out_offsets[0, m], whatever the alignment of d_out (to
+ * id_width it must be aligned, as d_ids; 16-byte stores are used where the address allows).
+ * BPE_E_ARG before any device work: id_width not 4 or 8, an unknown flag, BPE_SELECT_TAIL with max_len == 0, d_index =
+ * NULL with m > 0, d_ids = NULL with n > 0, d_doc_offsets or d_out_offsets NULL, a misaligned pointer.  BPE_E_LIMIT:
+ * n >= 2^32 (as for rows; it also makes every l_j and s_j fit 32 bits), m >= 2^32, n_docs >= 2^48; the total itself is
+ * 64-bit -- repetition can take it past 2^32.
+ * The placement is laid out by the output: "sel_tile" elements per workgroup, the output starts inside a tile staged in
+ * LDS ("sel_stage" of them; bpe_set_option).  Runs on the ctx's stream and synchronises it before returning; keeps no
+ * pointer of the caller's; only counters cross PCIe.  The lengths, their scan and the sources s_j are the ctx's decode
+ * scratch, shared with bpe_decode_batch: a result of that call not yet read is dropped.  The decode vocab table, the
+ * projection table and the count scratch are not touched. */
+#define BPE_SELECT_TAIL 1u
+int bpe_select_docs_resident(bpe_ctx *ctx, const void *d_ids, int32_t id_width, uint64_t n,
+                             const uint64_t *d_doc_offsets, uint64_t n_docs,
+                             const int64_t *d_index, uint64_t m,
+                             uint64_t max_len, uint32_t flags,
+                             void *d_out, uint64_t out_cap, uint64_t *d_out_offsets,
+                             uint64_t *n_out, uint64_t *bad_doc, uint64_t *bad_sel);
 
 /* ---- measurement ------------------------------------------------------------ */
 #define BPE_PROF_WIDEN 0

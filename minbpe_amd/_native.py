@@ -107,6 +107,8 @@ _SIGS = {
                                        C.POINTER(_u64)]),
     "bpe_count_resident": (C.c_int, [_p, _p, _i32, _u64, _p, _u64, _i32, C.POINTER(_u64)]),
     "bpe_count_fold": (C.c_int, [_p, _i32, _p, _u64, _i32, _p, _p]),
+    "bpe_select_docs_resident": (C.c_int, [_p, _p, _i32, _u64, _p, _u64, _p, _u64, _u64, C.c_uint32, _p, _u64, _p,
+                                           C.POINTER(_u64), C.POINTER(_u64), C.POINTER(_u64)]),
     "bpe_prof_reset": (C.c_int, [_p]),
     "bpe_prof_read": (C.c_int, [_p, _p, _p, _p]),
     "bpe_encode_uses_16bit": (C.c_int, [_p, C.c_int32]),
@@ -284,8 +286,17 @@ class RowsTooSmall(ValueError):
         self.needed = needed
 
 
+class BadSelection(IndexError):
+    """bpe_select_docs_resident met an index outside [0, n_docs); index = the lowest such position of the selection."""
+
+    def __init__(self, index, msg):
+        super().__init__(msg)
+        self.index = index
+
+
 ROWS_PACK, ROWS_PER_DOC = 0, 1
 ROWS_HAS_SEP, ROWS_TRUNC_LEFT, ROWS_PAD_LEFT = 1, 2, 4
+SELECT_TAIL = 1
 
 
 def _ptr(a):
@@ -697,6 +708,28 @@ class Engine:
         if rc == BPE_E_ARG and bad.value != 0xFFFFFFFFFFFFFFFF:
             raise InvalidToken(int(bad.value))
         self._check(rc)
+
+    # -- document selection ------------------------------------------------------------
+    def select_docs_resident(self, d_ids: int, id_width: int, n: int, d_doc_off: int, n_docs: int, d_index: int, m: int,
+                             max_len: int = 0, flags: int = 0, d_out: int = 0, out_cap: int = 0, d_ooff: int = 0) -> int:
+        """bpe_select_docs_resident: d_ids (n ids of id_width = 4 or 8 bytes), d_doc_off (n_docs + 1 uint64), d_index
+        (m int64 document numbers), d_out (room for out_cap ids of the same width; 0 = only count) and d_ooff (m + 1
+        uint64, always written when the call counts) are device addresses (e.g. torch tensor.data_ptr()).  max_len 0 =
+        whole documents, flags SELECT_TAIL = the last max_len ids of each.  Returns the number of ids selected.  Offsets
+        that descend or pass n raise BadDocOffsets(entry), an index outside [0, n_docs) BadSelection(position); too
+        little room raises OutputTooSmall."""
+        no, bad_doc, bad_sel = _u64(0), _u64(0), _u64(0)
+        rc = _lib.bpe_select_docs_resident(self._h, C.c_void_p(d_ids), id_width, n, C.c_void_p(d_doc_off), n_docs,
+                                           C.c_void_p(d_index), m, int(max_len), flags, C.c_void_p(d_out), out_cap,
+                                           C.c_void_p(d_ooff), C.byref(no), C.byref(bad_doc), C.byref(bad_sel))
+        if rc == BPE_E_ARG and bad_doc.value != 0xFFFFFFFFFFFFFFFF:
+            raise BadDocOffsets(int(bad_doc.value), (_lib.bpe_last_error(self._h) or b"").decode())
+        if rc == BPE_E_ARG and bad_sel.value != 0xFFFFFFFFFFFFFFFF:
+            raise BadSelection(int(bad_sel.value), (_lib.bpe_last_error(self._h) or b"").decode())
+        if rc == BPE_E_CAP:
+            raise OutputTooSmall(int(no.value), (_lib.bpe_last_error(self._h) or b"").decode())
+        self._check(rc)
+        return int(no.value)
 
     # -- measurement ----------------------------------------------------------------
     def prof_reset(self):

@@ -16,7 +16,8 @@ constexpr int SCRATCH_WORDS = 8;  // what bpe_create allocates
 union ScratchWords {
     // bpe_get_stats, bpe_read_stats, bpe_read_chunk_starts, spans_meta, the resident encode's offset check
     unsigned long long count;
-    struct {  // resident_two_pass (bpe_decode_batch_resident, bpe_project_resident); bpe_decode_batch: the first two
+    struct {  // resident_two_pass (bpe_decode_batch_resident, bpe_project_resident, bpe_select_docs_resident after its
+              // offsets check, which borrows `rows`); bpe_decode_batch: the first two
         unsigned long long bad, total, docbad;
     } two_pass;
     struct {  // bpe_token_spans_resident: read back as one block
@@ -331,6 +332,9 @@ struct bpe_ctx {
     // bpe_rows_resident (k_rows.hip)
     int rows_tile = 4096;    // option "rows_tile": output elements per workgroup tile
     int rows_stage = 1024;   // option "rows_stage": document starts a tile stages in LDS (0: every lane searches global memory, the cross-check form)
+    // bpe_select_docs_resident (k_seldocs.hip)
+    int sel_tile = 4096;     // option "sel_tile": output elements per workgroup tile
+    int sel_stage = 1024;    // option "sel_stage": output starts a tile stages in LDS (0: every lane searches global memory, the cross-check form)
     // bpe_token_spans_resident (k_spans.hip): leads | cont << 31 of every table entry, made on the device by the first
     // call after a bpe_decode_set_vocab; the second scan channel and the documents' bases (grow-only)
     DevPtr<uint32_t> d_dec_meta;

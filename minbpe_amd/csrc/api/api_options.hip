@@ -97,11 +97,14 @@ const OptRow OPTIONS[] = {
 };
 
 // The rows that came after tests/native/ctx_check.hip pinned the table above at the 57 it walks one by one: the same
-// rows, looked up after it.  The id histogram (bpe_count_resident): bins, ids
+// rows, looked up after it.  The id histogram (bpe_count_resident): bins, ids; document selection
+// (bpe_select_docs_resident): elements, output starts
 const OptRow OPTIONS_MORE[] = {
     OPT_STEP(count_lds_bins, 256, COUNT_LDS_BINS_MAX, 256),
     OPT(count_flush, 64, 1ll << 31),
     OPT_ON(count_combine),
+    OPT_STEP(sel_tile, 64, SEL_TILE_MAX, 4),
+    OPT(sel_stage, 0, SEL_STAGE_MAX),
 };
 
 #undef OPT_RAW

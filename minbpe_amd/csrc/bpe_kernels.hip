@@ -66,4 +66,5 @@
 #include "kernels/k_spans.hip"
 #include "kernels/k_project.hip"
 #include "kernels/k_count.hip"
+#include "kernels/k_seldocs.hip"
 #include "kernels/k_util.hip"

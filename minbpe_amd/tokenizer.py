@@ -625,6 +625,105 @@ class Tokenizer:
         pairs, arr = self._host_counts(counts)
         return _native.count_fold(pairs, arr, None, want_curve=True)[1]
 
+    # -- which documents, in what order: gather, filter, shuffle -----------
+    @staticmethod
+    def _select_values(max_len, keep):
+        """(max_len, flags) of the library from the keywords; ValueError for values it does not know"""
+        if keep not in ("head", "tail"):
+            raise ValueError(f"keep={keep!r} not understood: 'head' or 'tail'")
+        if max_len is None:
+            return 0, 0
+        if isinstance(max_len, bool) or not isinstance(max_len, (int, np.integer)) or max_len < 1:
+            raise ValueError("max_len must be a positive integer or None")
+        return min(int(max_len), 2**64 - 1), _native.SELECT_TAIL if keep == "tail" else 0
+
+    @staticmethod
+    def _select_index(index, n_docs, dev):
+        """`index` as select_docs_resident states it -> a 1-D int64 tensor on `dev` (its upload happens here), checked as
+        far as that needs no look at the values: TypeError for anything but integers or a mask, or more than one
+        dimension; ValueError for a mask that does not have n_docs entries."""
+        import torch
+        if isinstance(index, torch.Tensor):
+            if index.device != dev:
+                raise TypeError("index must be on the device of ids (or a sequence on the host)")
+            if index.dtype not in (torch.bool, torch.int32, torch.int64):
+                raise TypeError("index must hold int64 or int32 document numbers, or be a bool mask")
+            if index.dim() != 1:
+                raise TypeError("index must be 1-D")
+            if index.dtype == torch.bool:
+                if index.numel() != n_docs:
+                    raise ValueError(f"the mask holds {index.numel()} entries, there are {n_docs} documents")
+                return torch.nonzero(index).reshape(-1)
+            return index.to(torch.int64).contiguous()
+        arr = np.asarray(index)
+        if arr.size and arr.dtype.kind not in "iub":
+            raise TypeError("index must hold integers (or be a bool mask)")
+        if arr.ndim > 1:
+            raise TypeError("index must be a flat sequence or a 1-D array")
+        arr = arr.reshape(-1)
+        if arr.dtype.kind == "b":
+            if arr.size != n_docs:
+                raise ValueError(f"the mask holds {arr.size} entries, there are {n_docs} documents")
+            arr = np.flatnonzero(arr)
+        elif arr.dtype.kind == "u" and arr.size and int(arr.max()) >= 2**63:
+            raise IndexError(f"index[{int(np.argmax(arr >= 2**63))}] names no document")
+        return torch.from_numpy(np.ascontiguousarray(arr.astype(np.int64, copy=False))).to(dev)
+
+    def select_docs_resident(self, ids, doc_offsets, index, *, max_len=None, keep="head", out=None):
+        """The documents `index` names, in its order, as a new id stream, made on the device: a shuffle, a filter or a
+        sample in front of rows_resident, decode_batch_resident, token_spans_resident, project_resident and the counts;
+        not in the reference.  `ids` is a 1-D contiguous int32 or int64 torch tensor on the GPU, `doc_offsets` n_docs + 1
+        token positions -- an integer tensor on the same GPU or anything np.asarray takes --, document d being
+        ids[doc_offsets[d]:doc_offsets[d + 1]].  index: a 1-D int64 or int32 tensor on that GPU; a bool tensor of exactly
+        n_docs entries there, which keeps those documents in order; or a sequence / array of integers on the host, which is
+        uploaded.  Documents may repeat, come in any order and be left out; a number outside [0, n_docs) -- a negative
+        one included: nothing wraps -- raises IndexError with the lowest such position.  max_len: keep at most that many
+        ids of each document, its head (keep="head") or its tail (keep="tail").
+
+        Returns (ids', doc_offsets'): the selected ids in the dtype of `ids`, and the int64 [len(index) + 1] offsets of
+        the selected documents in ids', both on the GPU.  out: a tensor like ids to select into (the view out[:total] is
+        returned; ValueError if it is too small); without it the selection is measured by a count-only call first.
+        Offsets that descend or pass len(ids) raise ValueError.  Nothing but counters crosses PCIe."""
+        import torch
+        max_len, flags = self._select_values(max_len, keep)
+        _check_ids(ids, (torch.int32, torch.int64), cuda=False)
+        dev = ids.device
+        doc_offsets = _check_doc_offsets(doc_offsets, dev, strict=True)
+        n_docs = (doc_offsets.numel() if isinstance(doc_offsets, torch.Tensor) else doc_offsets.size) - 1
+        if out is not None and (not isinstance(out, torch.Tensor) or out.device != dev or out.dtype != ids.dtype
+                                or out.dim() != 1 or not out.is_contiguous()):
+            raise TypeError("out must be a 1-D contiguous torch tensor of the dtype and on the device of ids")
+        idx = self._select_index(index, n_docs, dev)
+        _check_ids(ids, (torch.int32, torch.int64))
+        doff = _place_doc_offsets(doc_offsets, dev)
+        ooff = torch.empty(idx.numel() + 1, dtype=torch.int64, device=dev)
+        eng = engine(dev.index)
+        torch.cuda.current_stream(dev).synchronize()  # the caller's pending writes to ids (and uploads above) are done
+        res = self._resident_fill(
+            ids, out, ids.dtype, None, "ids", "selects",
+            lambda dst, cap, *_: eng.select_docs_resident(ids.data_ptr(), ids.element_size(), ids.numel(), doff.data_ptr(),
+                                                          n_docs, idx.data_ptr(), idx.numel(), max_len, flags, dst, cap,
+                                                          ooff.data_ptr()))
+        return res, ooff
+
+    def select_docs(self, ids, doc_offsets, index, *, device=None, **kw):
+        """select_docs_resident() for ids on the host (a list or an array of integers): NumPy (ids', doc_offsets'), the
+        ids int32 if an int32 array came in and int64 otherwise.  device: the GPU's index (default: the process-wide
+        engine's)."""
+        import torch
+        self._select_values(kw.get("max_len"), kw.get("keep", "head"))
+        if kw.get("out") is not None:
+            raise TypeError("select_docs makes its own output")
+        arr = np.asarray(ids)
+        arr = np.ascontiguousarray(arr) if arr.dtype == np.int32 and arr.ndim == 1 else _host_array(ids)
+        doc_offsets = _check_doc_offsets(doc_offsets, torch.device("cpu"), strict=True)
+        if isinstance(doc_offsets, torch.Tensor):
+            doc_offsets = doc_offsets.numpy()
+        # (its errors, before a device is named; a mask is resolved here, on the host)
+        index = self._select_index(index, doc_offsets.size - 1, torch.device("cpu")).numpy()
+        res, ooff = self.select_docs_resident(torch.from_numpy(arr).to(_cuda_device(device)), doc_offsets, index, **kw)
+        return res.cpu().numpy(), ooff.cpu().numpy()
+
     # -- fixed-length rows from ids that live in HBM (DESIGN 4.4) ---------------------
     def rows_resident(self, ids, doc_offsets, row_len, *, stride=None, sep=None, pad=0, mode="pack", truncate="right",
                       pad_side="right", dtype=None, drop_last=False, return_doc_index=False, return_positions=False,
