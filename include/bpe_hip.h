@@ -83,7 +83,11 @@ int bpe_set_stream(bpe_ctx *ctx, void *hip_stream);
  *   no faster);
  *   bpe_select_docs_resident's placement kernel: "sel_tile" (4096: output elements per workgroup tile, 64..65536, a
  *   multiple of 4), "sel_stage" (1024: output starts a tile stages in LDS, 0..4096; a tile that holds more searches
- *   global memory instead, and 0 makes every tile do so -- the cross-check form). */
+ *   global memory instead, and 0 makes every tile do so -- the cross-check form);
+ *   bpe_dup_docs_resident: "dup_tile" (4096: stream positions per workgroup tile of its hash pass, 64..65536, a multiple
+ *   of 4), "dup_wave_len" (64, 4..1024: a key of more ids than this is probed and compared by a whole wave, a shorter
+ *   one by its lane), "dup_hash_bits" (64, 0..64: only so many bits of a key's hash choose its first table slot and
+ *   spare comparisons; 0 makes every probe a full comparison -- the results are the same at every value). */
 int bpe_set_option(bpe_ctx *ctx, const char *name, int64_t value);
 
 /* ---- input ----------------------------------------------------------------- */
@@ -476,6 +480,44 @@ int bpe_select_docs_resident(bpe_ctx *ctx, const void *d_ids, int32_t id_width, 
                              uint64_t max_len, uint32_t flags,
                              void *d_out, uint64_t out_cap, uint64_t *d_out_offsets,
                              uint64_t *n_out, uint64_t *bad_doc, uint64_t *bad_sel);
+
+/* ---- document de-duplication: exact first copies, found in HBM -------- */
+/* Which documents of an id stream that lives in HBM are copies of an earlier one: the mask "keep one copy of each" that
+ * bpe_select_docs_resident takes, made without the ids leaving the device.  Every large buffer is ON THE DEVICE and
+ * owned by the caller.
+ *   key(d)           the slice bpe_select_docs_resident emits for document d with the same max_len and flags:
+ *                    ids[s_d : s_d + l_d], l_d = len(d) or min(len(d), max_len), s_d = off[d] or off[d + 1] - l_d
+ *   key(d) == key(e) the same length and the same ids at their full width: two int64 ids that differ only above bit 32
+ *                    differ; empty keys are equal to each other
+ *   first[d]         the lowest e with key(e) == key(d): first[d] <= d, first[first[d]] == first[d], and
+ *                    first[d] == d marks the copy to keep
+ *   counts[d]        the number of documents with d's key where first[d] == d, and 0 elsewhere
+ *   *n_distinct      the number of d with first[d] == d
+ * The result is exact and does not depend on scheduling: a hash of the key chooses where a table of document numbers
+ * is probed and spares comparisons, and every equality reported has been established by comparing the ids themselves.
+ *   d_ids, id_width  n ids of 4 (int32) or 8 (int64) bytes, read in place, never written
+ *   d_doc_offsets    validated on the device exactly as in bpe_rows_resident: ascending, none beyond n.  The first bad
+ *                    entry goes to *bad_doc (~0 if none), the call fails with BPE_E_ARG and nothing is written to
+ *                    d_first or d_counts
+ *   max_len, flags   as in bpe_select_docs_resident: 0 = whole documents, BPE_SELECT_TAIL = the last max_len ids
+ *   d_first          n_docs int64 words (NULL only with n_docs == 0)
+ *   d_counts         n_docs words, or NULL: not wanted
+ * n_docs == 0 is BPE_OK with *n_distinct = 0 and nothing written.
+ * BPE_E_ARG before any device work: id_width not 4 or 8, an unknown flag, BPE_SELECT_TAIL with max_len == 0, d_ids =
+ * NULL with n > 0, d_doc_offsets NULL, d_first NULL with n_docs > 0, a misaligned pointer (d_ids to id_width, the others
+ * to 8 bytes).  BPE_E_LIMIT, before anything is launched or allocated: n >= 2^32, n_docs >= 2^32 - 1 (document numbers
+ * are 32-bit words with ~0 for "none").
+ * Three passes (bpe_set_option: "dup_tile", "dup_wave_len", "dup_hash_bits"): the keys' hashes in one read of the
+ * stream, laid out by the ids and not by the documents; the insertion into an open-addressing table of the power of
+ * two >= 2 n_docs slots, with the full comparisons; first and counts.  Runs on the ctx's stream and synchronises it
+ * before returning; keeps no pointer of the caller's; only counters cross PCIe.  Its scratch (8 + 12 bytes per
+ * document and the table) is a group of its own, grow-only: no other call's pending result is touched -- unlike
+ * selection it leaves the decode scratch alone. */
+int bpe_dup_docs_resident(bpe_ctx *ctx, const void *d_ids, int32_t id_width, uint64_t n,
+                          const uint64_t *d_doc_offsets, uint64_t n_docs,
+                          uint64_t max_len, uint32_t flags,
+                          int64_t *d_first, uint64_t *d_counts,
+                          uint64_t *n_distinct, uint64_t *bad_doc);
 
 /* ---- measurement ------------------------------------------------------------ */
 #define BPE_PROF_WIDEN 0

@@ -109,6 +109,8 @@ _SIGS = {
     "bpe_count_fold": (C.c_int, [_p, _i32, _p, _u64, _i32, _p, _p]),
     "bpe_select_docs_resident": (C.c_int, [_p, _p, _i32, _u64, _p, _u64, _p, _u64, _u64, C.c_uint32, _p, _u64, _p,
                                            C.POINTER(_u64), C.POINTER(_u64), C.POINTER(_u64)]),
+    "bpe_dup_docs_resident": (C.c_int, [_p, _p, _i32, _u64, _p, _u64, _u64, C.c_uint32, _p, _p, C.POINTER(_u64),
+                                        C.POINTER(_u64)]),
     "bpe_prof_reset": (C.c_int, [_p]),
     "bpe_prof_read": (C.c_int, [_p, _p, _p, _p]),
     "bpe_encode_uses_16bit": (C.c_int, [_p, C.c_int32]),
@@ -730,6 +732,23 @@ class Engine:
             raise OutputTooSmall(int(no.value), (_lib.bpe_last_error(self._h) or b"").decode())
         self._check(rc)
         return int(no.value)
+
+    # -- document de-duplication -------------------------------------------------------
+    def dup_docs_resident(self, d_ids: int, id_width: int, n: int, d_doc_off: int, n_docs: int, max_len: int = 0,
+                          flags: int = 0, d_first: int = 0, d_counts: int = 0) -> int:
+        """bpe_dup_docs_resident: d_ids (n ids of id_width = 4 or 8 bytes), d_doc_off (n_docs + 1 uint64), d_first
+        (n_docs int64) and d_counts (n_docs uint64; 0 = not wanted) are device addresses (e.g. torch tensor.data_ptr()).
+        Documents are compared by the slices select_docs_resident emits for the same max_len and flags.  Returns the
+        number of distinct documents.  Offsets that descend or pass n raise BadDocOffsets(entry), and nothing is
+        written then."""
+        nd, bad_doc = _u64(0), _u64(0)
+        rc = _lib.bpe_dup_docs_resident(self._h, C.c_void_p(d_ids), id_width, n, C.c_void_p(d_doc_off), n_docs,
+                                        int(max_len), flags, C.c_void_p(d_first), C.c_void_p(d_counts), C.byref(nd),
+                                        C.byref(bad_doc))
+        if rc == BPE_E_ARG and bad_doc.value != 0xFFFFFFFFFFFFFFFF:
+            raise BadDocOffsets(int(bad_doc.value), (_lib.bpe_last_error(self._h) or b"").decode())
+        self._check(rc)
+        return int(nd.value)
 
     # -- measurement ----------------------------------------------------------------
     def prof_reset(self):

@@ -26,6 +26,9 @@ union ScratchWords {
     struct {  // bpe_rows_resident: read back as one block
         unsigned long long bad, ends[2];
     } rows;
+    struct {  // bpe_dup_docs_resident: `rows` for its offsets check, and the number of groups
+        unsigned long long bad, ends[2], distinct;
+    } dup;
     struct {  // bpe_count_resident: the first position whose id is in no bin
         unsigned long long bad;
     } hist;
@@ -335,6 +338,16 @@ struct bpe_ctx {
     // bpe_select_docs_resident (k_seldocs.hip)
     int sel_tile = 4096;     // option "sel_tile": output elements per workgroup tile
     int sel_stage = 1024;    // option "sel_stage": output starts a tile stages in LDS (0: every lane searches global memory, the cross-check form)
+    // bpe_dup_docs_resident (k_dupdocs.hip), a scratch of its own (grow-only): per document the sum of its key, its
+    // representative, and -- at the representative's number -- the group's lowest document and size; the open-addressing
+    // table of document numbers, the power of two >= 2 cap_dup_docs slots
+    DevPtr<unsigned long long> d_dup_hash;
+    DevPtr<uint32_t> d_dup_rep, d_dup_gmin, d_dup_cnt, d_dup_tab;
+    uint64_t cap_dup_docs = 0;
+    int dup_tile = 4096;      // option "dup_tile": stream positions per workgroup tile of the hash pass
+    int dup_wave_len = 64;    // option "dup_wave_len": keys of more ids than this are probed and compared by a whole wave, the others by one lane
+                              // (the fastest of 16, 32, 64, 128 on documents of 19 ids, level with 16 and 32 on documents of 190: DESIGN 4.9)
+    int dup_hash_bits = 64;   // option "dup_hash_bits": bits of the hash that choose the first slot and filter the comparisons (tests: 0 = none)
     // bpe_token_spans_resident (k_spans.hip): leads | cont << 31 of every table entry, made on the device by the first
     // call after a bpe_decode_set_vocab; the second scan channel and the documents' bases (grow-only)
     DevPtr<uint32_t> d_dec_meta;

@@ -98,13 +98,16 @@ const OptRow OPTIONS[] = {
 
 // The rows that came after tests/native/ctx_check.hip pinned the table above at the 57 it walks one by one: the same
 // rows, looked up after it.  The id histogram (bpe_count_resident): bins, ids; document selection
-// (bpe_select_docs_resident): elements, output starts
+// (bpe_select_docs_resident): elements, output starts; document de-duplication (bpe_dup_docs_resident): positions, ids, bits
 const OptRow OPTIONS_MORE[] = {
     OPT_STEP(count_lds_bins, 256, COUNT_LDS_BINS_MAX, 256),
     OPT(count_flush, 64, 1ll << 31),
     OPT_ON(count_combine),
     OPT_STEP(sel_tile, 64, SEL_TILE_MAX, 4),
     OPT(sel_stage, 0, SEL_STAGE_MAX),
+    OPT_STEP(dup_tile, 64, DUP_TILE_MAX, 4),
+    OPT(dup_wave_len, 4, DUP_WAVE_LEN_MAX),
+    OPT(dup_hash_bits, 0, 64),
 };
 
 #undef OPT_RAW

@@ -34,6 +34,27 @@ int ensure_dec_scratch(bpe_ctx *c, uint64_t n) {
     });
 }
 
+// The offsets of a document list, checked as bpe_rows_resident states them (k_rows_check, through the `rows` counter
+// words): BPE_E_ARG with *bad_doc = the first entry that descends or lies beyond n.  ends (may be null): off[0] and
+// off[n_docs] come to the host in the same transfer.  The stream is synchronised when it returns.
+int check_doc_offsets(bpe_ctx *c, const uint64_t *d_doc_offsets, uint64_t n_docs, uint64_t n, uint64_t *bad_doc,
+                      unsigned long long *ends) {
+    auto *w = &c->d_scratch->rows;
+    HIPCHK(c, hipMemsetAsync(&w->bad, 0xFF, sizeof(unsigned long long), c->stream));
+    hipLaunchKernelGGL(k_rows_check, dim3(grid_for(n_docs + 1, 256, c->num_cus * 8)), dim3(256), 0, c->stream,
+                       (const unsigned long long *)d_doc_offsets, n_docs, n, &w->bad, w->ends);
+    LAUNCHCHK(c, "k_rows_check");
+    unsigned long long hb[3] = {0, 0, 0};  // {first bad entry, off[0], off[n_docs]}
+    HIPCHK(c, hipMemcpyAsync(hb, &w->bad, (ends ? 3 : 1) * sizeof(unsigned long long), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    if (hb[0] != ~0ull) {
+        if (bad_doc) *bad_doc = hb[0];
+        return fail(c, BPE_E_ARG, "doc_offsets[%llu]: offsets must ascend and stay <= n = %llu", hb[0], (unsigned long long)n);
+    }
+    if (ends) ends[0] = hb[1], ends[1] = hb[2];
+    return BPE_OK;
+}
+
 // what a user of resident_two_pass says besides its two launches
 struct TwoPassText {
     const char *bad_fmt;  // the message of an id the length pass refused: one %llu, its position

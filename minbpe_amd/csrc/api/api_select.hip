@@ -30,20 +30,7 @@ extern "C" int bpe_select_docs_resident(bpe_ctx *c, const void *d_ids, int32_t i
     if (m >= (1ull << 32)) return fail(c, BPE_E_LIMIT, "%llu selections exceed 2^32-1", (unsigned long long)m);
     if (n_docs >= (1ull << 48)) return fail(c, BPE_E_LIMIT, "%llu documents exceed 2^48-1", (unsigned long long)n_docs);
     HIPCHK(c, hipSetDevice(c->device));
-    {
-        auto *w = &c->d_scratch->rows;
-        HIPCHK(c, hipMemsetAsync(&w->bad, 0xFF, sizeof(unsigned long long), c->stream));
-        hipLaunchKernelGGL(k_rows_check, dim3(grid_for(n_docs + 1, 256, c->num_cus * 8)), dim3(256), 0, c->stream,
-                           (const unsigned long long *)d_doc_offsets, n_docs, n, &w->bad, w->ends);
-        LAUNCHCHK(c, "k_rows_check");
-        unsigned long long hb = 0;
-        HIPCHK(c, hipMemcpyAsync(&hb, &w->bad, sizeof hb, hipMemcpyDeviceToHost, c->stream));
-        HIPCHK(c, hipStreamSynchronize(c->stream));
-        if (hb != ~0ull) {
-            if (bad_doc) *bad_doc = hb;
-            return fail(c, BPE_E_ARG, "doc_offsets[%llu]: offsets must ascend and stay <= n = %llu", hb, (unsigned long long)n);
-        }
-    }
+    TRY(check_doc_offsets(c, d_doc_offsets, n_docs, n, bad_doc, nullptr));
     // from here on the offsets are known to ascend inside [0, n]: every s_j, l_j of the length pass lies inside the ids
     const uint32_t tail = (flags & BPE_SELECT_TAIL) ? 1u : 0u;
     // (the scratch pointers are read inside the two launches: resident_two_pass has grown the scratch by then)

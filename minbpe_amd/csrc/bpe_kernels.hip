@@ -67,4 +67,5 @@
 #include "kernels/k_project.hip"
 #include "kernels/k_count.hip"
 #include "kernels/k_seldocs.hip"
+#include "kernels/k_dupdocs.hip"
 #include "kernels/k_util.hip"

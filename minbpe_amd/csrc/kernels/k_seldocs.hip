@@ -20,6 +20,37 @@ constexpr uint32_t SEL_V = 8;             // consecutive output elements per lan
 constexpr uint32_t SEL_TILE_MAX = 65536;  // (distances inside a tile fit 32 bits with room to spare)
 constexpr uint32_t SEL_STAGE_MAX = 4096;  // output starts a tile stages in LDS, 4 bytes each (relative to the tile's first)
 
+// What goes on of the document ids[o0 : o1): its length l and its first position s.  The one statement of the rule
+// above: bpe_dup_docs_resident (k_dupdocs.hip) compares documents by the same slices.
+__device__ __forceinline__ void seldocs_slice(unsigned long long o0, unsigned long long o1, unsigned long long max_len,
+                                              uint32_t tail, uint32_t &l, uint32_t &s) {
+    const unsigned long long L = o1 - o0, lj = max_len ? min(L, max_len) : L;
+    l = (uint32_t)lj;
+    s = (uint32_t)(tail ? o1 - lj : o0);
+}
+
+// j = upper_bound(oo, e) - 1 over the m + 1 ascending entries oo[0] <= e < oo[m], by one wave (e is the same in all its
+// lanes), 64 probes at a time: log64(m) dependent loads where a lane on its own would wait for log2(m)
+__device__ __forceinline__ unsigned long long seldocs_wave_search(const unsigned long long *oo, unsigned long long m,
+                                                                  unsigned long long e, uint32_t lane) {
+    unsigned long long lo = 1, hi = m;  // the first j in [lo, hi] with oo[j] > e: oo[m] > e
+    // bound: log64(m) + 2 rounds -- a round leaves at most span / 64 + 1 of the span, and a span below 64 is probed at every
+    // entry; lo and hi come from the ballot, the same in all lanes
+    while (lo < hi) {
+        const unsigned long long base = lo, span = hi - lo;
+        const unsigned long long p = base + ((span * lane) >> 6);  // base = p_0 <= ... <= p_63 < hi
+        const unsigned long long beyond = __ballot(oo[p] > e);     // (oo ascends: a suffix of the lanes)
+        if (beyond == 0) {
+            lo = base + ((span * 63) >> 6) + 1;
+        } else {
+            const uint32_t f = (uint32_t)__ffsll(beyond) - 1;
+            hi = base + ((span * f) >> 6);
+            if (f) lo = base + ((span * (f - 1)) >> 6) + 1;
+        }
+    }
+    return lo - 1;
+}
+
 // Length pass, one selection per thread.  The offsets have passed k_rows_check (ascending, none beyond n < 2^32), so l_j
 // and s_j fit 32 bits.  An index is compared at its full 64 bits; bad = the lowest j whose index lies outside [0, n_docs).
 __global__ void __launch_bounds__(256)
@@ -33,10 +64,7 @@ k_seldocs_len(const unsigned long long *__restrict__ off, uint64_t n_docs, const
         if (d < 0 || (unsigned long long)d >= n_docs) {
             atomicMin(bad, (unsigned long long)j);
         } else {
-            const unsigned long long o0 = off[d], o1 = off[d + 1];
-            const unsigned long long L = o1 - o0, lj = max_len ? min(L, max_len) : L;
-            l = (uint32_t)lj;
-            s = (uint32_t)(tail ? o1 - lj : o0);
+            seldocs_slice(off[d], off[d + 1], max_len, tail, l, s);
         }
         len[j] = l;
         src[j] = s;
@@ -105,24 +133,9 @@ k_seldocs_place(const SelArgs A) {
         const unsigned long long e_lo = max(g0, a) - a, e_hi = g1 - a;  // the tile's elements: [e_lo, e_hi), never empty
         __syncthreads();  // (the staging area of the tile before is free)
         if (tid < 128) {
-            // waves 0 and 1, one for e_lo and one for e_hi - 1: j = upper_bound(oo, e) - 1 over ALL selections, 64 probes
-            // at a time -- log64(m) dependent loads where a lane on its own would wait for log2(m)
-            const uint32_t lane = tid & 63;
-            const unsigned long long e = tid < 64 ? e_lo : e_hi - 1;
-            unsigned long long lo = 1, hi = A.m;  // the first j in [lo, hi] with oo[j] > e: oo[m] = total > e
-            while (lo < hi) {  // (lo and hi come from the ballot: the same in all lanes)
-                const unsigned long long base = lo, span = hi - lo;
-                const unsigned long long p = base + ((span * lane) >> 6);  // base = p_0 <= ... <= p_63 < hi
-                const unsigned long long beyond = __ballot(oo[p] > e);     // (oo ascends: a suffix of the lanes)
-                if (beyond == 0) {
-                    lo = base + ((span * 63) >> 6) + 1;
-                } else {
-                    const uint32_t f = (uint32_t)__ffsll(beyond) - 1;
-                    hi = base + ((span * f) >> 6);
-                    if (f) lo = base + ((span * (f - 1)) >> 6) + 1;
-                }
-            }
-            if (lane == 0) s_sel[tid >> 6] = lo - 1;
+            // waves 0 and 1, one for e_lo and one for e_hi - 1, over ALL selections: oo[m] = total > e
+            const unsigned long long j = seldocs_wave_search(oo, A.m, tid < 64 ? e_lo : e_hi - 1, tid & 63);
+            if ((tid & 63) == 0) s_sel[tid >> 6] = j;
         }
         __syncthreads();
         const unsigned long long j_lo = s_sel[0], j_hi = s_sel[1];

@@ -724,6 +724,82 @@ class Tokenizer:
         res, ooff = self.select_docs_resident(torch.from_numpy(arr).to(_cuda_device(device)), doc_offsets, index, **kw)
         return res.cpu().numpy(), ooff.cpu().numpy()
 
+    # -- which documents are copies of an earlier one ----------------------
+    @property
+    def n_distinct_docs(self):
+        """The number of distinct documents the last duplicate_docs_resident() / unique_docs_resident() of this
+        tokenizer found (and their host forms); None before the first.  Read-only: it came back as a counter."""
+        return getattr(self, "_n_distinct_docs", None)
+
+    def duplicate_docs_resident(self, ids, doc_offsets, *, max_len=None, keep="head", return_counts=False):
+        """For every document the number of its first copy, found on the device: first[d] = the lowest e whose document
+        equals document d -- the same length and the same ids at their full width; not in the reference.  first[d] <= d,
+        first[first] == first, and first == arange(n_docs) is the mask "keep one copy of each" that select_docs_resident
+        takes.  `ids` and `doc_offsets` are what select_docs_resident takes.  max_len / keep: documents are compared by
+        what select_docs_resident would emit for them with the same values -- their first (keep="head") or last
+        (keep="tail") max_len ids.  Exact: a hash only chooses where to look, every equality is established by
+        comparing the ids; the result does not depend on scheduling.
+
+        Returns first, an int64 tensor [n_docs] on the device of `ids`; with return_counts=True (first, counts), counts
+        int64 [n_docs]: the number of copies at every d with first[d] == d and 0 elsewhere.  n_distinct_docs then holds
+        the number of distinct documents.  Offsets that descend or pass len(ids) raise ValueError.  Nothing but counters
+        crosses PCIe."""
+        import torch
+        max_len, flags = self._select_values(max_len, keep)
+        _check_ids(ids, (torch.int32, torch.int64), cuda=False)
+        dev = ids.device
+        doc_offsets = _check_doc_offsets(doc_offsets, dev, strict=True)
+        _check_ids(ids, (torch.int32, torch.int64))
+        doff = _place_doc_offsets(doc_offsets, dev)
+        n_docs = doff.numel() - 1
+        first = torch.empty(n_docs, dtype=torch.int64, device=dev)
+        counts = torch.empty(n_docs, dtype=torch.int64, device=dev) if return_counts else None
+        eng = engine(dev.index)
+        torch.cuda.current_stream(dev).synchronize()  # the caller's pending writes to ids (and the upload above) are done
+        self._n_distinct_docs = eng.dup_docs_resident(ids.data_ptr(), ids.element_size(), ids.numel(), doff.data_ptr(),
+                                                      n_docs, max_len, flags, first.data_ptr(),
+                                                      counts.data_ptr() if return_counts else 0)
+        return (first, counts) if return_counts else first
+
+    def unique_docs_resident(self, ids, doc_offsets, *, max_len=None, keep="head", out=None):
+        """One copy of every document, the first, in the order of the stream: duplicate_docs_resident() and
+        select_docs_resident() over first == arange in one call.  Returns (ids', doc_offsets', index, counts): the id
+        stream of the kept documents and its offsets as select_docs_resident returns them, index int64 [k] the kept
+        document numbers and counts int64 [k] how many copies each had, all on the device of `ids`.  With max_len the
+        kept documents are cut the same way they were compared.  out: as in select_docs_resident."""
+        import torch
+        first, counts = self.duplicate_docs_resident(ids, doc_offsets, max_len=max_len, keep=keep, return_counts=True)
+        index = torch.nonzero(first == torch.arange(first.numel(), dtype=torch.int64, device=first.device)).reshape(-1)
+        res, ooff = self.select_docs_resident(ids, doc_offsets, index, max_len=max_len, keep=keep, out=out)
+        return res, ooff, index, counts[index]
+
+    def _host_docs(self, ids, doc_offsets, device, kw):
+        """the arguments of duplicate_docs / unique_docs, checked before a device is named -> (ids on the GPU, offsets)"""
+        import torch
+        self._select_values(kw.get("max_len"), kw.get("keep", "head"))
+        arr = np.asarray(ids)
+        arr = np.ascontiguousarray(arr) if arr.dtype == np.int32 and arr.ndim == 1 else _host_array(ids)
+        doc_offsets = _check_doc_offsets(doc_offsets, torch.device("cpu"), strict=True)
+        if isinstance(doc_offsets, torch.Tensor):
+            doc_offsets = doc_offsets.numpy()
+        return torch.from_numpy(arr).to(_cuda_device(device)), doc_offsets
+
+    def duplicate_docs(self, ids, doc_offsets, *, device=None, **kw):
+        """duplicate_docs_resident() for ids on the host (a list or an array of integers; an int32 array is compared as
+        int32, anything else as int64): NumPy first, or (first, counts).  device: the GPU's index (default: the
+        process-wide engine's)."""
+        d_ids, doc_offsets = self._host_docs(ids, doc_offsets, device, kw)
+        res = self.duplicate_docs_resident(d_ids, doc_offsets, **kw)
+        return tuple(t.cpu().numpy() for t in res) if isinstance(res, tuple) else res.cpu().numpy()
+
+    def unique_docs(self, ids, doc_offsets, *, device=None, **kw):
+        """unique_docs_resident() for ids on the host: NumPy (ids', doc_offsets', index, counts), the ids int32 if an
+        int32 array came in and int64 otherwise."""
+        if kw.get("out") is not None:
+            raise TypeError("unique_docs makes its own output")
+        d_ids, doc_offsets = self._host_docs(ids, doc_offsets, device, kw)
+        return tuple(t.cpu().numpy() for t in self.unique_docs_resident(d_ids, doc_offsets, **kw))
+
     # -- fixed-length rows from ids that live in HBM (DESIGN 4.4) ---------------------
     def rows_resident(self, ids, doc_offsets, row_len, *, stride=None, sep=None, pad=0, mode="pack", truncate="right",
                       pad_side="right", dtype=None, drop_last=False, return_doc_index=False, return_positions=False,
