@@ -87,7 +87,10 @@ int bpe_set_stream(bpe_ctx *ctx, void *hip_stream);
  *   bpe_dup_docs_resident: "dup_tile" (4096: stream positions per workgroup tile of its hash pass, 64..65536, a multiple
  *   of 4), "dup_wave_len" (64, 4..1024: a key of more ids than this is probed and compared by a whole wave, a shorter
  *   one by its lane), "dup_hash_bits" (64, 0..64: only so many bits of a key's hash choose its first table slot and
- *   spare comparisons; 0 makes every probe a full comparison -- the results are the same at every value). */
+ *   spare comparisons; 0 makes every probe a full comparison -- the results are the same at every value);
+ *   bpe_minhash_resident's signature pass: "mh_tile" (2048: stream positions per workgroup tile, a power of two from
+ *   64 to 65536; a tile goes through LDS 2048 positions at a time, a smaller tile whole -- the results are the same at
+ *   every value). */
 int bpe_set_option(bpe_ctx *ctx, const char *name, int64_t value);
 
 /* ---- input ----------------------------------------------------------------- */
@@ -518,6 +521,76 @@ int bpe_dup_docs_resident(bpe_ctx *ctx, const void *d_ids, int32_t id_width, uin
                           uint64_t max_len, uint32_t flags,
                           int64_t *d_first, uint64_t *d_counts,
                           uint64_t *n_distinct, uint64_t *bad_doc);
+
+/* ---- near-duplicate documents: MinHash signatures, made in HBM -------- */
+/* The MinHash signature of every document of an id stream that lives in HBM: n_perm int32 words per document, such
+ * that the share of positions at which two rows agree estimates the Jaccard similarity of the two documents' sets of
+ * ngram-id windows.  Banding the rows (bpe_dup_docs_resident on d_sig as an int32 stream) finds candidates,
+ * bpe_minhash_agree_resident verifies them, and the result is a `first` column that bpe_select_docs_resident takes: all
+ * without the ids leaving the device.  Every large buffer is ON THE DEVICE and owned by the caller.  All arithmetic is
+ * unsigned; "& M32" is mod 2^32.
+ *   fmix32(h)        h ^= h >> 16; h = h * 0x85EBCA6B & M32; h ^= h >> 13; h = h * 0xC2B2AE35 & M32; h ^= h >> 16
+ *   tok(x)           x sign-extended to 64 bits (an int32 id and the int64 id of the same value hash alike; two int64
+ *                    ids that differ only above bit 32 do not): lo = x & M32, hi = x >> 32;
+ *                    tok = fmix32(lo ^ (hi * 0x9E3779B1 & M32))
+ *   key(d)           the slice bpe_select_docs_resident emits for document d with the same max_len and flags, length l
+ *   shingles(d)      window w = ngram.  l == 0: none.  ww = min(w, l); m = l - ww + 1 shingles; for i in [0, m):
+ *                    s = 0; for k in [0, ww): s = (s * 0x01000193 + tok(key[i + k])) & M32;
+ *                    S_i = fmix32(s ^ ((seed ^ ww) & M32)).  A key shorter than the window is ONE shingle, all of it;
+ *                    a shingle never crosses a document's end, nor the end of the key where max_len cuts it
+ *   A_p, B_p         z = seed; for p in [0, n_perm): A_p = next() | 1, B_p = next(); next() is splitmix64:
+ *                    z = z + 0x9E3779B97F4A7C15; r = z; r = (r ^ r >> 30) * 0xBF58476D1CE4E5B9;
+ *                    r = (r ^ r >> 27) * 0x94D049BB133111EB; return r ^ r >> 31 (all mod 2^64).  Made on the host and
+ *                    uploaded, at most 16 KiB
+ *   sig[d][p]        min_i ((A_p * S_i + B_p) mod 2^64) >> 33: a value in [0, 2^31), an int32 that is never negative;
+ *                    no shingle (an empty key): 0x7FFFFFFF for every p
+ * The result does not depend on scheduling: a minimum is the same in whatever order its terms are folded.
+ *   d_ids, id_width  n ids of 4 (int32) or 8 (int64) bytes, read in place, never written
+ *   d_doc_offsets    validated on the device exactly as in bpe_rows_resident: ascending, none beyond n.  The first bad
+ *                    entry goes to *bad_doc (~0 if none), the call fails with BPE_E_ARG and nothing is written to d_sig.
+ *                    Ids before off[0] or at or after off[n_docs], and ids beyond max_len, enter no shingle
+ *   max_len, flags   as in bpe_select_docs_resident: 0 = whole documents, BPE_SELECT_TAIL = the last max_len ids
+ *   ngram            1..64
+ *   n_perm           1..1024; it need not be a multiple of 64
+ *   d_sig, sig_cap   int32 [n_docs][n_perm], row-major; sig_cap = the words there is room for (NULL only with
+ *                    n_docs == 0).  sig_cap < n_docs * n_perm fails with BPE_E_CAP and nothing is written
+ * n_docs == 0 is BPE_OK with nothing written.
+ * BPE_E_ARG before any device work: id_width not 4 or 8, an unknown flag, BPE_SELECT_TAIL with max_len == 0, ngram
+ * outside [1, 64], n_perm outside [1, 1024], d_ids = NULL with n > 0, d_doc_offsets NULL, d_sig NULL with n_docs > 0, a
+ * misaligned pointer (d_ids to id_width, d_doc_offsets to 8 bytes, d_sig to 4).  BPE_E_LIMIT, before anything is
+ * launched or allocated: n >= 2^32, n_docs >= 2^32 - 1, n_docs * n_perm >= 2^40.
+ * Never writes a word outside d_sig[0, n_docs * n_perm).
+ * Two passes (bpe_set_option: "mh_tile"): the rows of empty keys, and of keys whose shingles lie in more than one strip
+ * of the next pass, are set to 0x7FFFFFFF; then one read of the stream, laid out by the ids and not by the documents --
+ * per tile the shingle that starts at every position goes to LDS, and every wave walks a strip of them with a
+ * permutation per lane: a key inside one strip is one plain store per word, the others fold by atomicMin.  Runs on the
+ * ctx's stream and synchronises it before returning; keeps no pointer of the caller's; only the parameters and counters
+ * cross PCIe.  Its scratch (16 n_perm bytes) is a group of its own, grow-only: the decode scratch and every other
+ * call's pending result are left alone. */
+int bpe_minhash_resident(bpe_ctx *ctx, const void *d_ids, int32_t id_width, uint64_t n,
+                         const uint64_t *d_doc_offsets, uint64_t n_docs,
+                         uint64_t max_len, uint32_t flags,
+                         uint32_t ngram, uint32_t n_perm, uint64_t seed,
+                         int32_t *d_sig, uint64_t sig_cap,
+                         uint64_t *bad_doc);
+/* At how many positions two signatures agree: agree[j] = #{p : sig[a_j][p] == sig[b_j][p]}, for m pairs of rows of a
+ * signature matrix in HBM; agree[j] / n_perm estimates the Jaccard similarity of documents a_j and b_j.
+ *   d_sig            int32 [n_docs][n_perm], row-major, read in place, never written
+ *   d_a, d_b, m      m int64 document numbers each, in [0, n_docs), compared at their full 64 bits (a negative one does
+ *                    not wrap); a_j == b_j and repeated pairs are fine.  The lowest j at which a_j or b_j is outside
+ *                    goes to *bad_pair (~0 if none), the call fails with BPE_E_ARG and nothing is written to d_agree
+ *   d_agree          m int32 words
+ * m == 0 is BPE_OK with nothing written.
+ * BPE_E_ARG before any device work: n_perm outside [1, 1024]; with m > 0, d_a, d_b or d_agree NULL, or d_sig NULL with
+ * n_docs > 0; a misaligned pointer (d_sig and d_agree to 4 bytes, d_a and d_b to 8).  BPE_E_LIMIT: n_docs >= 2^32 - 1,
+ * n_docs * n_perm >= 2^40.
+ * Never writes a word outside d_agree[0, m).  16 lanes per pair, 16-byte loads where n_perm % 4 == 0 and d_sig is
+ * 16-byte aligned.  Runs on the ctx's stream and synchronises it before returning; keeps no pointer of the caller's;
+ * only a counter crosses PCIe; no scratch besides that counter. */
+int bpe_minhash_agree_resident(bpe_ctx *ctx, const int32_t *d_sig, uint64_t n_docs, uint32_t n_perm,
+                               const int64_t *d_a, const int64_t *d_b, uint64_t m,
+                               int32_t *d_agree,
+                               uint64_t *bad_pair);
 
 /* ---- measurement ------------------------------------------------------------ */
 #define BPE_PROF_WIDEN 0

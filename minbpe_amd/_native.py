@@ -111,6 +111,9 @@ _SIGS = {
                                            C.POINTER(_u64), C.POINTER(_u64), C.POINTER(_u64)]),
     "bpe_dup_docs_resident": (C.c_int, [_p, _p, _i32, _u64, _p, _u64, _u64, C.c_uint32, _p, _p, C.POINTER(_u64),
                                         C.POINTER(_u64)]),
+    "bpe_minhash_resident": (C.c_int, [_p, _p, _i32, _u64, _p, _u64, _u64, C.c_uint32, C.c_uint32, C.c_uint32, _u64, _p,
+                                       _u64, C.POINTER(_u64)]),
+    "bpe_minhash_agree_resident": (C.c_int, [_p, _p, _u64, C.c_uint32, _p, _p, _u64, _p, C.POINTER(_u64)]),
     "bpe_prof_reset": (C.c_int, [_p]),
     "bpe_prof_read": (C.c_int, [_p, _p, _p, _p]),
     "bpe_encode_uses_16bit": (C.c_int, [_p, C.c_int32]),
@@ -290,6 +293,14 @@ class RowsTooSmall(ValueError):
 
 class BadSelection(IndexError):
     """bpe_select_docs_resident met an index outside [0, n_docs); index = the lowest such position of the selection."""
+
+    def __init__(self, index, msg):
+        super().__init__(msg)
+        self.index = index
+
+
+class BadPair(IndexError):
+    """bpe_minhash_agree_resident met a pair that names no document; index = the lowest such position of the pairs."""
 
     def __init__(self, index, msg):
         super().__init__(msg)
@@ -749,6 +760,35 @@ class Engine:
             raise BadDocOffsets(int(bad_doc.value), (_lib.bpe_last_error(self._h) or b"").decode())
         self._check(rc)
         return int(nd.value)
+
+    # -- near-duplicate documents ------------------------------------------------------
+    def minhash_resident(self, d_ids: int, id_width: int, n: int, d_doc_off: int, n_docs: int, max_len: int = 0,
+                         flags: int = 0, ngram: int = 5, n_perm: int = 128, seed: int = 0, d_sig: int = 0,
+                         sig_cap: int = 0):
+        """bpe_minhash_resident: d_ids (n ids of id_width = 4 or 8 bytes), d_doc_off (n_docs + 1 uint64) and d_sig (room
+        for sig_cap >= n_docs * n_perm int32 words) are device addresses (e.g. torch tensor.data_ptr()).  Documents are
+        cut as select_docs_resident cuts them for the same max_len and flags.  Offsets that descend or pass n raise
+        BadDocOffsets(entry), too little room raises OutputTooSmall; nothing is written then."""
+        bad_doc = _u64(0)
+        rc = _lib.bpe_minhash_resident(self._h, C.c_void_p(d_ids), id_width, n, C.c_void_p(d_doc_off), n_docs, int(max_len),
+                                       flags, ngram, n_perm, int(seed) & 0xFFFFFFFFFFFFFFFF, C.c_void_p(d_sig), sig_cap,
+                                       C.byref(bad_doc))
+        if rc == BPE_E_ARG and bad_doc.value != 0xFFFFFFFFFFFFFFFF:
+            raise BadDocOffsets(int(bad_doc.value), (_lib.bpe_last_error(self._h) or b"").decode())
+        if rc == BPE_E_CAP:
+            raise OutputTooSmall(n_docs * n_perm, (_lib.bpe_last_error(self._h) or b"").decode())
+        self._check(rc)
+
+    def minhash_agree_resident(self, d_sig: int, n_docs: int, n_perm: int, d_a: int, d_b: int, m: int, d_agree: int):
+        """bpe_minhash_agree_resident: d_sig (int32 [n_docs][n_perm]), d_a and d_b (m int64 document numbers each) and
+        d_agree (m int32) are device addresses.  A pair outside [0, n_docs) raises BadPair(position), and nothing is
+        written then."""
+        bad = _u64(0)
+        rc = _lib.bpe_minhash_agree_resident(self._h, C.c_void_p(d_sig), n_docs, n_perm, C.c_void_p(d_a), C.c_void_p(d_b),
+                                             m, C.c_void_p(d_agree), C.byref(bad))
+        if rc == BPE_E_ARG and bad.value != 0xFFFFFFFFFFFFFFFF:
+            raise BadPair(int(bad.value), (_lib.bpe_last_error(self._h) or b"").decode())
+        self._check(rc)
 
     # -- measurement ----------------------------------------------------------------
     def prof_reset(self):

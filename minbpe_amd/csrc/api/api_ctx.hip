@@ -32,6 +32,9 @@ union ScratchWords {
     struct {  // bpe_count_resident: the first position whose id is in no bin
         unsigned long long bad;
     } hist;
+    struct {  // bpe_minhash_agree_resident: the first pair that names no document (bpe_minhash_resident: `rows`)
+        unsigned long long bad;
+    } mh;
     struct {  // encode_batch_impl (min_rank and starts: the stream-wide rounds of its longest chunks)
         unsigned long long nlong, total;
         uint32_t min_rank, pad;
@@ -348,6 +351,13 @@ struct bpe_ctx {
     int dup_wave_len = 64;    // option "dup_wave_len": keys of more ids than this are probed and compared by a whole wave, the others by one lane
                               // (the fastest of 16, 32, 64, 128 on documents of 19 ids, level with 16 and 32 on documents of 190: DESIGN 4.9)
     int dup_hash_bits = 64;   // option "dup_hash_bits": bits of the hash that choose the first slot and filter the comparisons (tests: 0 = none)
+    // bpe_minhash_resident (k_minhash.hip), a scratch of its own (grow-only): A_p | B_p of the permutations, as made from
+    // (mh_seed, mh_perm) -- mh_perm == 0: of nothing yet
+    DevPtr<unsigned long long> d_mh_ab;
+    uint64_t cap_mh_perm = 0, mh_seed = 0;
+    uint32_t mh_perm = 0;
+    int mh_tile = 2048;       // option "mh_tile": stream positions per workgroup tile of the signature pass, a power of two (the fastest of
+                              // 256 .. 65536 on documents of 19 ids: DESIGN 4.10)
     // bpe_token_spans_resident (k_spans.hip): leads | cont << 31 of every table entry, made on the device by the first
     // call after a bpe_decode_set_vocab; the second scan channel and the documents' bases (grow-only)
     DevPtr<uint32_t> d_dec_meta;

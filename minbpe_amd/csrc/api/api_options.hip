@@ -8,6 +8,7 @@ namespace {
 
 enum OptKind {
     OPT_RANGE,  // lo <= value <= hi and value % step == 0, stored as is
+    OPT_POW2,   // lo <= value <= hi and value a power of two, stored as is
     OPT_FLAG,   // any value, stored as value != 0
     OPT_ANY,    // any value, stored as is (cast to the field's type)
 };
@@ -98,7 +99,8 @@ const OptRow OPTIONS[] = {
 
 // The rows that came after tests/native/ctx_check.hip pinned the table above at the 57 it walks one by one: the same
 // rows, looked up after it.  The id histogram (bpe_count_resident): bins, ids; document selection
-// (bpe_select_docs_resident): elements, output starts; document de-duplication (bpe_dup_docs_resident): positions, ids, bits
+// (bpe_select_docs_resident): elements, output starts; document de-duplication (bpe_dup_docs_resident): positions, ids, bits;
+// MinHash signatures (bpe_minhash_resident): positions
 const OptRow OPTIONS_MORE[] = {
     OPT_STEP(count_lds_bins, 256, COUNT_LDS_BINS_MAX, 256),
     OPT(count_flush, 64, 1ll << 31),
@@ -108,6 +110,7 @@ const OptRow OPTIONS_MORE[] = {
     OPT_STEP(dup_tile, 64, DUP_TILE_MAX, 4),
     OPT(dup_wave_len, 4, DUP_WAVE_LEN_MAX),
     OPT(dup_hash_bits, 0, 64),
+    OPT_NAMED("mh_tile", mh_tile, OPT_POW2, 64, MH_TILE_MAX, 1),
 };
 
 #undef OPT_RAW
@@ -131,6 +134,8 @@ extern "C" int bpe_set_option(bpe_ctx *c, const char *name, int64_t value) {
             if (o.hi == INT64_MAX) return fail(c, BPE_E_ARG, "%s: %lld or more", o.name, (long long)o.lo);
             return fail(c, BPE_E_ARG, "%s: %lld..%lld", o.name, (long long)o.lo, (long long)o.hi);
         }
+        if (o.kind == OPT_POW2 && (value < o.lo || value > o.hi || (value & (value - 1))))
+            return fail(c, BPE_E_ARG, "%s: %lld..%lld, a power of two", o.name, (long long)o.lo, (long long)o.hi);
         o.set(c, o.kind == OPT_FLAG ? (int64_t)(value != 0) : value);
         return BPE_OK;
     }

@@ -68,4 +68,5 @@
 #include "kernels/k_count.hip"
 #include "kernels/k_seldocs.hip"
 #include "kernels/k_dupdocs.hip"
+#include "kernels/k_minhash.hip"
 #include "kernels/k_util.hip"

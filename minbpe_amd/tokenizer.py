@@ -9,6 +9,7 @@ encoding runs on the GPU through the C-ABI in include/bpe_hip.h.  Host Python
 only does what the reference leaves to the `regex` module and to O(vocab)
 bookkeeping ("out of scope as kernels").
 """
+import math
 import os
 import unicodedata
 
@@ -799,6 +800,176 @@ class Tokenizer:
             raise TypeError("unique_docs makes its own output")
         d_ids, doc_offsets = self._host_docs(ids, doc_offsets, device, kw)
         return tuple(t.cpu().numpy() for t in self.unique_docs_resident(d_ids, doc_offsets, **kw))
+
+    # -- which documents are nearly copies of an earlier one --------------
+    @staticmethod
+    def _minhash_values(n_perm, ngram):
+        """ValueError for a number of permutations or a window the library does not take"""
+        for name, v, hi in (("n_perm", n_perm, 1024), ("ngram", ngram, 64)):
+            if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or not 1 <= v <= hi:
+                raise ValueError(f"{name} must be an integer from 1 to {hi}")
+        return int(n_perm), int(ngram)
+
+    @staticmethod
+    def _minhash_seed(seed):
+        if isinstance(seed, bool) or not isinstance(seed, (int, np.integer)) or not 0 <= seed < 2**64:
+            raise ValueError("seed must be an integer from 0 to 2^64 - 1")
+        return int(seed)
+
+    def minhash_resident(self, ids, doc_offsets, *, n_perm=128, ngram=5, seed=0, max_len=None, keep="head", out=None):
+        """The MinHash signature of every document, made on the device; not in the reference.  `ids` and `doc_offsets`
+        are what select_docs_resident takes.  A document is the set of its windows of `ngram` consecutive ids (one shorter
+        than the window: the one window that is all of it); row d of the result holds, for each of n_perm hash functions
+        made from `seed`, the smallest hash among document d's windows, so that the share of positions at which two rows
+        agree estimates the Jaccard similarity of the two sets (standard error about sqrt(J (1 - J) / n_perm)).  An
+        int32 id and the int64 id of the same value hash alike.  max_len / keep: documents are cut as
+        select_docs_resident cuts them with the same values.  n_perm 1..1024, ngram 1..64.  The definition is in
+        include/bpe_hip.h; the result does not depend on scheduling.
+
+        Returns sig, an int32 tensor [n_docs, n_perm] on the device of `ids`; a document without ids is a row of
+        0x7FFFFFFF.  out: a contiguous int32 tensor of at least n_docs * n_perm elements on the same GPU to write into
+        (the view of the rows written is returned; ValueError if it is too small).  Offsets that descend or pass
+        len(ids) raise ValueError.  Nothing but the hash parameters and counters crosses PCIe."""
+        import torch
+        max_len, flags = self._select_values(max_len, keep)
+        n_perm, ngram = self._minhash_values(n_perm, ngram)
+        seed = self._minhash_seed(seed)
+        _check_ids(ids, (torch.int32, torch.int64), cuda=False)
+        dev = ids.device
+        doc_offsets = _check_doc_offsets(doc_offsets, dev, strict=True)
+        n_docs = (doc_offsets.numel() if isinstance(doc_offsets, torch.Tensor) else doc_offsets.size) - 1
+        if out is not None:
+            if not isinstance(out, torch.Tensor) or out.device != dev or out.dtype != torch.int32 or not out.is_contiguous():
+                raise TypeError("out must be a contiguous int32 torch tensor on the device of ids")
+            if out.numel() < n_docs * n_perm:
+                raise ValueError(f"out holds {out.numel()} elements, the signatures need {n_docs * n_perm}")
+        _check_ids(ids, (torch.int32, torch.int64))
+        doff = _place_doc_offsets(doc_offsets, dev)
+        if out is None:
+            out = torch.empty(n_docs * n_perm, dtype=torch.int32, device=dev)
+        eng = engine(dev.index)
+        torch.cuda.current_stream(dev).synchronize()  # the caller's pending writes to ids (and the upload above) are done
+        eng.minhash_resident(ids.data_ptr(), ids.element_size(), ids.numel(), doff.data_ptr(), n_docs, max_len, flags,
+                             ngram, n_perm, seed, out.data_ptr(), out.numel())
+        return out.reshape(-1)[:n_docs * n_perm].view(n_docs, n_perm)
+
+    def minhash(self, ids, doc_offsets, *, device=None, **kw):
+        """minhash_resident() for ids on the host (a list or an array of integers; an int32 array goes up as int32,
+        anything else as int64 -- the signatures are the same): NumPy int32 [n_docs, n_perm].  device: the GPU's index
+        (default: the process-wide engine's)."""
+        self._minhash_values(kw.get("n_perm", 128), kw.get("ngram", 5))
+        self._minhash_seed(kw.get("seed", 0))
+        if kw.get("out") is not None:
+            raise TypeError("minhash makes its own output")
+        d_ids, doc_offsets = self._host_docs(ids, doc_offsets, device, kw)
+        return self.minhash_resident(d_ids, doc_offsets, **kw).cpu().numpy()
+
+    def minhash_agreement_resident(self, sig, a, b):
+        """At how many positions rows a[j] and b[j] of a signature matrix agree, counted on the device: int32 [m];
+        divided by n_perm, the estimate of the two documents' Jaccard similarity.  `sig` is what minhash_resident
+        returned (a contiguous int32 [n_docs, n_perm] tensor on the GPU); a and b are equally long 1-D int64 or int32
+        tensors on that GPU, or sequences of integers on the host, which are uploaded.  An index outside [0, n_docs) --
+        a negative one included: nothing wraps -- raises IndexError with the lowest such position."""
+        import torch
+        if not isinstance(sig, torch.Tensor) or sig.dim() != 2 or sig.dtype != torch.int32 or not sig.is_contiguous():
+            raise TypeError("sig must be a contiguous int32 [n_docs, n_perm] torch tensor on the GPU")
+        n_docs, n_perm = sig.shape
+        self._minhash_values(n_perm, 1)
+        dev = sig.device
+        pairs = [self._select_index(x, n_docs, dev) if not (isinstance(x, torch.Tensor) and x.dtype == torch.bool)
+                 else None for x in (a, b)]
+        if pairs[0] is None or pairs[1] is None:
+            raise TypeError("a and b must hold int64 or int32 document numbers")
+        if pairs[0].numel() != pairs[1].numel():
+            raise ValueError(f"a holds {pairs[0].numel()} documents and b {pairs[1].numel()}")
+        if not sig.is_cuda:
+            raise TypeError("sig must be a contiguous int32 [n_docs, n_perm] torch tensor on the GPU")
+        agree = torch.empty(pairs[0].numel(), dtype=torch.int32, device=dev)
+        eng = engine(dev.index)
+        torch.cuda.current_stream(dev).synchronize()  # the caller's pending writes to sig (and the uploads above) are done
+        eng.minhash_agree_resident(sig.data_ptr(), n_docs, n_perm, pairs[0].data_ptr(), pairs[1].data_ptr(),
+                                   pairs[0].numel(), agree.data_ptr())
+        return agree
+
+    @staticmethod
+    def _near_values(threshold, n_perm, bands):
+        """(rows per band, agreeing positions needed) from the keywords; ValueError for values that make no banding"""
+        if isinstance(bands, bool) or not isinstance(bands, (int, np.integer)) or bands < 1 or n_perm % bands:
+            raise ValueError("bands must be a positive integer that divides n_perm")
+        if isinstance(threshold, bool) or not isinstance(threshold, (int, float, np.integer, np.floating)) \
+                or not 0 < threshold <= 1:
+            raise ValueError("threshold must be a number in (0, 1]")
+        return n_perm // int(bands), int(math.ceil(float(threshold) * n_perm))
+
+    def near_duplicate_docs_resident(self, ids, doc_offsets, *, threshold=0.8, n_perm=128, bands=32, ngram=5, seed=0,
+                                     max_len=None, keep="head", return_signatures=False):
+        """For every document the lowest document number of its group of near-duplicates, found on the device: MinHash
+        signatures (minhash_resident), locality-sensitive banding, verification, connected components; not in the
+        reference.  The signature is cut into `bands` bands of n_perm / bands positions.  In every band a document is a
+        candidate for the FIRST document whose band equals its own (duplicate_docs_resident on the signatures), and the
+        two are joined if their whole signatures agree at ceil(threshold * n_perm) positions or more
+        (minhash_agreement_resident); first[d] is the lowest document of d's connected component.  A candidate is verified
+        against the first document of its bucket only: that is the definition.  Documents without ids form one group.
+        first[d] <= d, first[first] == first, and first == arange(n_docs) is the mask "keep one document of each group"
+        that select_docs_resident takes.  Exact copies are always in one group, so the result is coarser than or equal
+        to duplicate_docs_resident's.  The other arguments are minhash_resident's; n_docs * n_perm must stay below 2^32.
+
+        Returns first, an int64 tensor [n_docs] on the device of `ids`; with return_signatures=True (first, sig).
+        n_distinct_docs then holds the number of groups.  Nothing but hash parameters and counters crosses PCIe."""
+        import torch
+        max_len_v, _ = self._select_values(max_len, keep)
+        n_perm, ngram = self._minhash_values(n_perm, ngram)
+        seed = self._minhash_seed(seed)
+        rows, need = self._near_values(threshold, n_perm, bands)
+        _check_ids(ids, (torch.int32, torch.int64), cuda=False)
+        dev = ids.device
+        doc_offsets = _check_doc_offsets(doc_offsets, dev, strict=True)
+        n_docs = (doc_offsets.numel() if isinstance(doc_offsets, torch.Tensor) else doc_offsets.size) - 1
+        if n_docs * n_perm >= 2**32:
+            raise ValueError(f"{n_docs} documents of {n_perm} positions: the signatures must stay below 2^32 words")
+        _check_ids(ids, (torch.int32, torch.int64))
+        sig = self.minhash_resident(ids, doc_offsets, n_perm=n_perm, ngram=ngram, seed=seed, max_len=max_len, keep=keep)
+        arange = torch.arange(n_docs, dtype=torch.int64, device=dev)
+        flat = sig.view(-1)
+        band_off = torch.arange(n_docs + 1, dtype=torch.int64, device=dev) * n_perm
+        labels = arange.clone()
+        edges_a, edges_b = [], []
+        for band in range(n_perm // rows):
+            # document d of this stream is sig[d, band * rows : (band + 1) * rows] and nothing else
+            off_b = torch.clamp(band_off + band * rows, max=n_docs * n_perm)
+            first_b = self.duplicate_docs_resident(flat, off_b, max_len=rows)
+            cand = torch.nonzero(first_b != arange).reshape(-1)
+            if cand.numel() == 0:
+                continue
+            rep = first_b[cand]
+            ok = self.minhash_agreement_resident(sig, cand, rep) >= need
+            edges_a.append(cand[ok])
+            edges_b.append(rep[ok])
+        if edges_a:
+            ea, eb = torch.cat(edges_a), torch.cat(edges_b)
+            # min-label propagation with pointer jumping: a label only ever decreases and names a document of the same
+            # component, so this ends, at the component's lowest document
+            while ea.numel():
+                low = torch.minimum(labels[ea], labels[eb])
+                new = labels.clone()
+                new.scatter_reduce_(0, ea, low, "amin")
+                new.scatter_reduce_(0, eb, low, "amin")
+                new = new[new]
+                if torch.equal(new, labels):
+                    break
+                labels = new
+        self._n_distinct_docs = int((labels == arange).sum())
+        return (labels, sig) if return_signatures else labels
+
+    def near_duplicate_docs(self, ids, doc_offsets, *, device=None, **kw):
+        """near_duplicate_docs_resident() for ids on the host (a list or an array of integers): NumPy first, or
+        (first, sig).  device: the GPU's index (default: the process-wide engine's)."""
+        n_perm, _ = self._minhash_values(kw.get("n_perm", 128), kw.get("ngram", 5))
+        self._minhash_seed(kw.get("seed", 0))
+        self._near_values(kw.get("threshold", 0.8), n_perm, kw.get("bands", 32))
+        d_ids, doc_offsets = self._host_docs(ids, doc_offsets, device, kw)
+        res = self.near_duplicate_docs_resident(d_ids, doc_offsets, **kw)
+        return tuple(t.cpu().numpy() for t in res) if isinstance(res, tuple) else res.cpu().numpy()
 
     # -- fixed-length rows from ids that live in HBM (DESIGN 4.4) ---------------------
     def rows_resident(self, ids, doc_offsets, row_len, *, stride=None, sep=None, pad=0, mode="pack", truncate="right",
