@@ -90,7 +90,12 @@ int bpe_set_stream(bpe_ctx *ctx, void *hip_stream);
  *   spare comparisons; 0 makes every probe a full comparison -- the results are the same at every value);
  *   bpe_minhash_resident's signature pass: "mh_tile" (2048: stream positions per workgroup tile, a power of two from
  *   64 to 65536; a tile goes through LDS 2048 positions at a time, a smaller tile whole -- the results are the same at
- *   every value). */
+ *   every value);
+ *   bpe_ngram_index_resident / bpe_ngram_overlap_resident's window pass: "ng_tile" (4096: stream positions per workgroup
+ *   tile, a power of two from 64 to 65536; a tile goes through LDS 2048 positions at a time, a smaller tile whole),
+ *   "ng_hash_bits" (64, 0..64: only so many bits of a window's hash choose its first table slot and its tag; 0 makes
+ *   every window start at slot 0 and every probe a full comparison; an index keeps the value it was built with -- the
+ *   results are the same at every value). */
 int bpe_set_option(bpe_ctx *ctx, const char *name, int64_t value);
 
 /* ---- input ----------------------------------------------------------------- */
@@ -591,6 +596,78 @@ int bpe_minhash_agree_resident(bpe_ctx *ctx, const int32_t *d_sig, uint64_t n_do
                                const int64_t *d_a, const int64_t *d_b, uint64_t m,
                                int32_t *d_agree,
                                uint64_t *bad_pair);
+
+/* ---- n-gram overlap: documents that share a window with a held-out set -------- */
+/* Decontamination: which documents of an id stream in HBM contain a window of w = ngram consecutive ids that also
+ * occurs in a reference stream (benchmarks, eval splits, a block list).  bpe_ngram_index_resident makes the ctx's index
+ * of the reference windows, bpe_ngram_overlap_resident looks every window of a corpus up in it.  Every large buffer is ON
+ * THE DEVICE and owned by the caller.  The definition (tests/ngram_model.py is its executable form):
+ *   reference        R [n_ref] with roff [n_ref_docs + 1].  For every reference document r and every i with
+ *   windows          roff[r] <= i and i + w <= roff[r + 1], the tuple R[i : i + w) is a reference window.  A reference
+ *                    document shorter than w contributes nothing; ids outside [roff[0], roff[n_ref_docs]) contribute nothing
+ *   equality         two windows are equal when they hold the same ids at their full width, by value: an int32 id and
+ *                    the int64 id of the same value are equal, two int64 ids that differ only above bit 32 are not;
+ *                    negative ids are values like any other
+ *   low(W)           for every distinct reference window W, the lowest stream position i at which it starts
+ *   key(d)           the slice bpe_select_docs_resident emits for document d of ids [n], off [n_docs + 1] with the same
+ *                    max_len and flags: start s_d, length l_d
+ *   hits             a window of the key starts at every key position k with k + w <= l_d; it is a hit if it equals
+ *                    some reference window.  A key shorter than w has no window (it is not shortened)
+ *   hits[d]          the number of hit positions (0 when the key has no window or the index is empty)
+ *   first[d]         (s_d - off[d]) + k for the lowest hit k, -1 when there is none: a position inside the uncut document
+ *   ref_pos[d]       low(W) for the window W at that first hit, -1 when there is none: an absolute position in R
+ *   starts[p]        uint8, 1 where a hit window starts at stream position p and 0 at every other of the n positions
+ * Exact, and the result does not depend on scheduling: a hash only chooses where to look, every equality is established
+ * by comparing ids, counts are sums and first / ref_pos are minima.
+ *
+ * bpe_ngram_index_resident builds the ctx's ONE n-gram index, replacing any earlier one.  The ctx keeps its own copy of
+ * the reference ids, sign-extended to 64 bits, so that a corpus of either width is compared by value: the caller may free
+ * its buffers when the call returns.
+ *   d_ref_ids, id_width  n_ref ids of 4 (int32) or 8 (int64) bytes, read in place, never written
+ *   d_ref_offsets    validated on the device exactly as in bpe_rows_resident: ascending, none beyond n_ref.  The first
+ *                    bad entry goes to *bad_doc (~0 if none) and the call fails with BPE_E_ARG
+ *   ngram            1..64
+ *   *index_id        a non-zero number, new for every successful build on this ctx (required)
+ *   *n_windows       the reference windows, repeats counted;  *n_distinct: the distinct ones (either may be NULL)
+ * An index without a window (n_ref_docs == 0, every reference document shorter than ngram) is valid.  A call that
+ * fails, for whatever reason, leaves the ctx WITHOUT an index.
+ * BPE_E_ARG before any device work: id_width not 4 or 8, ngram outside [1, 64], d_ref_ids = NULL with n_ref > 0,
+ * d_ref_offsets or index_id NULL, a misaligned pointer (d_ref_ids to id_width, d_ref_offsets to 8 bytes).  BPE_E_LIMIT,
+ * before anything is launched or allocated: n_ref >= 2^32, n_ref_docs >= 2^32 - 1.
+ * Passes (bpe_set_option: "ng_tile", "ng_hash_bits"): the copy; then the window pass over it -- laid out by the stream,
+ * the ids of a tile and their halo in LDS, a lane per position -- which puts every window into an open-addressing table
+ * of more than twice as many slots, a power of two: a slot is claimed by atomicCAS with tag << 32 | position and holds
+ * that for good, repeats fold their position into the slot's lowest by atomicMin.  The index (8 n_ref bytes and 12 per
+ * slot) is a scratch group of its own, grow-only: no other entry point touches it, it survives every other call on the
+ * ctx and is freed with it.  Only the counters {first bad entry, roff[0], roff[n_ref_docs]}, {windows, distinct} cross PCIe.
+ *
+ * bpe_ngram_overlap_resident:
+ *   index_id         must be the ctx's current index, otherwise BPE_E_STATE: 0, a replaced index, and any id after a
+ *                    failed rebuild
+ *   d_ids, id_width  n ids of 4 or 8 bytes -- either width against an index of either --, read in place, never written
+ *   d_doc_offsets    validated as above; the first bad entry goes to *bad_doc, BPE_E_ARG, nothing is written
+ *   max_len, flags   as in bpe_select_docs_resident: 0 = whole documents, BPE_SELECT_TAIL = the last max_len ids
+ *   d_hits           int64 [n_docs] (NULL only with n_docs == 0);  d_first, d_ref_pos: int64 [n_docs], each may be NULL
+ *   d_starts         uint8 [n], may be NULL; all n bytes are written
+ *   *n_hit_docs      the documents with hits > 0
+ * n_docs == 0 is BPE_OK with nothing written but d_starts.
+ * BPE_E_ARG before any device work: id_width not 4 or 8, an unknown flag, BPE_SELECT_TAIL with max_len == 0, d_ids =
+ * NULL with n > 0, d_doc_offsets NULL, d_hits NULL with n_docs > 0, a misaligned pointer (d_ids to id_width, the others
+ * but d_starts to 8 bytes).  BPE_E_LIMIT: n >= 2^32, n_docs >= 2^32 - 1.  Nothing is written to any output before the
+ * last check has passed.
+ * The same window pass over the corpus, the table read-only: per position the window's hash, then the probe -- an empty
+ * slot means no hit, a slot whose tag agrees is compared id by id, the window's own ids from LDS against the index's
+ * 64-bit copy.  Per document the hits fold by atomicAdd and (first, ref_pos) together by one 64-bit atomicMin on
+ * first << 32 | low; a last small pass unpacks into the caller's columns.  Runs on the ctx's stream and synchronises it
+ * before returning; keeps no pointer of the caller's; only the counters {first bad entry, off[0], off[n_docs]},
+ * {n_hit_docs} cross PCIe.  Its rows (12 bytes per document) are a scratch group of their own, grow-only. */
+int bpe_ngram_index_resident(bpe_ctx *ctx, const void *d_ref_ids, int32_t id_width, uint64_t n_ref,
+                             const uint64_t *d_ref_offsets, uint64_t n_ref_docs, uint32_t ngram,
+                             uint64_t *index_id, uint64_t *n_windows, uint64_t *n_distinct, uint64_t *bad_doc);
+int bpe_ngram_overlap_resident(bpe_ctx *ctx, uint64_t index_id, const void *d_ids, int32_t id_width, uint64_t n,
+                               const uint64_t *d_doc_offsets, uint64_t n_docs, uint64_t max_len, uint32_t flags,
+                               int64_t *d_hits, int64_t *d_first, int64_t *d_ref_pos, uint8_t *d_starts,
+                               uint64_t *n_hit_docs, uint64_t *bad_doc);
 
 /* ---- measurement ------------------------------------------------------------ */
 #define BPE_PROF_WIDEN 0

@@ -114,6 +114,10 @@ _SIGS = {
     "bpe_minhash_resident": (C.c_int, [_p, _p, _i32, _u64, _p, _u64, _u64, C.c_uint32, C.c_uint32, C.c_uint32, _u64, _p,
                                        _u64, C.POINTER(_u64)]),
     "bpe_minhash_agree_resident": (C.c_int, [_p, _p, _u64, C.c_uint32, _p, _p, _u64, _p, C.POINTER(_u64)]),
+    "bpe_ngram_index_resident": (C.c_int, [_p, _p, _i32, _u64, _p, _u64, C.c_uint32, C.POINTER(_u64), C.POINTER(_u64),
+                                           C.POINTER(_u64), C.POINTER(_u64)]),
+    "bpe_ngram_overlap_resident": (C.c_int, [_p, _u64, _p, _i32, _u64, _p, _u64, _u64, C.c_uint32, _p, _p, _p, _p,
+                                             C.POINTER(_u64), C.POINTER(_u64)]),
     "bpe_prof_reset": (C.c_int, [_p]),
     "bpe_prof_read": (C.c_int, [_p, _p, _p, _p]),
     "bpe_encode_uses_16bit": (C.c_int, [_p, C.c_int32]),
@@ -789,6 +793,38 @@ class Engine:
         if rc == BPE_E_ARG and bad.value != 0xFFFFFFFFFFFFFFFF:
             raise BadPair(int(bad.value), (_lib.bpe_last_error(self._h) or b"").decode())
         self._check(rc)
+
+    # -- n-gram overlap with a reference set -------------------------------------------
+    def ngram_index_resident(self, d_ref_ids: int, id_width: int, n_ref: int, d_ref_off: int, n_ref_docs: int,
+                             ngram: int = 13):
+        """bpe_ngram_index_resident: d_ref_ids (n_ref ids of id_width = 4 or 8 bytes) and d_ref_off (n_ref_docs + 1
+        uint64) are device addresses (e.g. torch tensor.data_ptr()); the engine keeps its own copy, and ONE index: this
+        one replaces any earlier one.  Returns (index_id, n_windows, n_distinct).  Offsets that descend or pass n_ref
+        raise BadDocOffsets(entry); a call that fails leaves the engine without an index."""
+        iid, nw, nd, bad_doc = _u64(0), _u64(0), _u64(0), _u64(0)
+        rc = _lib.bpe_ngram_index_resident(self._h, C.c_void_p(d_ref_ids), id_width, n_ref, C.c_void_p(d_ref_off),
+                                           n_ref_docs, ngram, C.byref(iid), C.byref(nw), C.byref(nd), C.byref(bad_doc))
+        if rc == BPE_E_ARG and bad_doc.value != 0xFFFFFFFFFFFFFFFF:
+            raise BadDocOffsets(int(bad_doc.value), (_lib.bpe_last_error(self._h) or b"").decode())
+        self._check(rc)
+        return int(iid.value), int(nw.value), int(nd.value)
+
+    def ngram_overlap_resident(self, index_id: int, d_ids: int, id_width: int, n: int, d_doc_off: int, n_docs: int,
+                               max_len: int = 0, flags: int = 0, d_hits: int = 0, d_first: int = 0, d_ref_pos: int = 0,
+                               d_starts: int = 0) -> int:
+        """bpe_ngram_overlap_resident: d_ids (n ids of id_width = 4 or 8 bytes), d_doc_off (n_docs + 1 uint64), d_hits
+        and, where wanted (0 = not), d_first and d_ref_pos (n_docs int64 each) and d_starts (n uint8) are device
+        addresses.  Documents are cut as select_docs_resident cuts them for the same max_len and flags.  Returns the
+        number of documents with a hit.  Offsets that descend or pass n raise BadDocOffsets(entry), an index_id that is
+        not the engine's current index raises RuntimeError; nothing is written then."""
+        nh, bad_doc = _u64(0), _u64(0)
+        rc = _lib.bpe_ngram_overlap_resident(self._h, index_id, C.c_void_p(d_ids), id_width, n, C.c_void_p(d_doc_off),
+                                             n_docs, int(max_len), flags, C.c_void_p(d_hits), C.c_void_p(d_first),
+                                             C.c_void_p(d_ref_pos), C.c_void_p(d_starts), C.byref(nh), C.byref(bad_doc))
+        if rc == BPE_E_ARG and bad_doc.value != 0xFFFFFFFFFFFFFFFF:
+            raise BadDocOffsets(int(bad_doc.value), (_lib.bpe_last_error(self._h) or b"").decode())
+        self._check(rc)
+        return int(nh.value)
 
     # -- measurement ----------------------------------------------------------------
     def prof_reset(self):

@@ -35,6 +35,10 @@ union ScratchWords {
     struct {  // bpe_minhash_agree_resident: the first pair that names no document (bpe_minhash_resident: `rows`)
         unsigned long long bad;
     } mh;
+    struct {  // bpe_ngram_index_resident, bpe_ngram_overlap_resident: `rows` for their offsets checks, {windows, distinct
+              // windows} of a build, the documents with a hit of a query
+        unsigned long long bad, ends[2], counts[2], hit_docs;
+    } ng;
     struct {  // encode_batch_impl (min_rank and starts: the stream-wide rounds of its longest chunks)
         unsigned long long nlong, total;
         uint32_t min_rank, pad;
@@ -358,6 +362,22 @@ struct bpe_ctx {
     uint32_t mh_perm = 0;
     int mh_tile = 2048;       // option "mh_tile": stream positions per workgroup tile of the signature pass, a power of two (the fastest of
                               // 256 .. 65536 on documents of 19 ids: DESIGN 4.10)
+    // bpe_ngram_index_resident (k_ngram.hip): the ctx's ONE n-gram index, a scratch of its own (grow-only) that no other
+    // entry point touches: the reference sign-extended to 64 bits, the open-addressing table of ng_slots slots (tag << 32
+    // | position) and the lowest position per slot.  ng_id: the number of the index that stands (0: none), ng_serial: the
+    // last number given out; ng_w, ng_bits: the window and the hash bits it was built with
+    DevPtr<long long> d_ng_ref;
+    DevPtr<unsigned long long> d_ng_tab;
+    DevPtr<uint32_t> d_ng_low;
+    uint64_t cap_ng_ref = 0, ng_id = 0, ng_serial = 0, ng_windows = 0, ng_slots = 0;
+    uint32_t ng_w = 0, ng_bits = 64;
+    // bpe_ngram_overlap_resident: per document the hit count and first << 32 | ref_pos, a group of their own (grow-only)
+    DevPtr<uint32_t> d_ng_cnt;
+    DevPtr<unsigned long long> d_ng_min;
+    uint64_t cap_ng_docs = 0;
+    int ng_tile = 4096;       // option "ng_tile": stream positions per workgroup tile of the window pass, a power of two (the fastest of
+                              // 256 .. 65536 on documents of 19 ids: DESIGN 4.11)
+    int ng_hash_bits = 64;    // option "ng_hash_bits": bits of the window hash that choose the first slot and the tag (tests: 0 = none)
     // bpe_token_spans_resident (k_spans.hip): leads | cont << 31 of every table entry, made on the device by the first
     // call after a bpe_decode_set_vocab; the second scan channel and the documents' bases (grow-only)
     DevPtr<uint32_t> d_dec_meta;

@@ -100,7 +100,8 @@ const OptRow OPTIONS[] = {
 // The rows that came after tests/native/ctx_check.hip pinned the table above at the 57 it walks one by one: the same
 // rows, looked up after it.  The id histogram (bpe_count_resident): bins, ids; document selection
 // (bpe_select_docs_resident): elements, output starts; document de-duplication (bpe_dup_docs_resident): positions, ids, bits;
-// MinHash signatures (bpe_minhash_resident): positions
+// MinHash signatures (bpe_minhash_resident): positions; n-gram overlap (bpe_ngram_index_resident,
+// bpe_ngram_overlap_resident): positions, bits
 const OptRow OPTIONS_MORE[] = {
     OPT_STEP(count_lds_bins, 256, COUNT_LDS_BINS_MAX, 256),
     OPT(count_flush, 64, 1ll << 31),
@@ -111,6 +112,8 @@ const OptRow OPTIONS_MORE[] = {
     OPT(dup_wave_len, 4, DUP_WAVE_LEN_MAX),
     OPT(dup_hash_bits, 0, 64),
     OPT_NAMED("mh_tile", mh_tile, OPT_POW2, 64, MH_TILE_MAX, 1),
+    OPT_NAMED("ng_tile", ng_tile, OPT_POW2, 64, NG_TILE_MAX, 1),
+    OPT(ng_hash_bits, 0, 64),
 };
 
 #undef OPT_RAW

@@ -69,4 +69,5 @@
 #include "kernels/k_seldocs.hip"
 #include "kernels/k_dupdocs.hip"
 #include "kernels/k_minhash.hip"
+#include "kernels/k_ngram.hip"
 #include "kernels/k_util.hip"

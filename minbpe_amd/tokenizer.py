@@ -164,6 +164,21 @@ def _place_doc_offsets(doc_offsets, dev):
     return torch.from_numpy(np.ascontiguousarray(doc_offsets, dtype=np.int64).reshape(-1)).to(dev)
 
 
+class NgramIndex:
+    """What Tokenizer.ngram_index_resident returns: the name of the n-gram index an engine holds.  ngram: the window;
+    n_windows: the reference windows, repeats counted; n_distinct: the distinct ones; device: the torch.device of the GPU
+    it lives on; id: the engine's number of this build.  An engine holds ONE index: the next build replaces it, and this
+    object then raises RuntimeError when it is used."""
+    __slots__ = ("ngram", "n_windows", "n_distinct", "device", "id")
+
+    def __init__(self, ngram, n_windows, n_distinct, device, id):
+        self.ngram, self.n_windows, self.n_distinct, self.device, self.id = ngram, n_windows, n_distinct, device, id
+
+    def __repr__(self):
+        return (f"NgramIndex(ngram={self.ngram}, n_windows={self.n_windows}, n_distinct={self.n_distinct}, "
+                f"device={str(self.device)!r}, id={self.id})")
+
+
 class Tokenizer:
     """Base class: state, vocab construction, save/load (base.py:66-165)."""
 
@@ -778,12 +793,19 @@ class Tokenizer:
         """the arguments of duplicate_docs / unique_docs, checked before a device is named -> (ids on the GPU, offsets)"""
         import torch
         self._select_values(kw.get("max_len"), kw.get("keep", "head"))
+        arr, doc_offsets = self._host_stream(ids, doc_offsets)
+        return torch.from_numpy(arr).to(_cuda_device(device)), doc_offsets
+
+    @staticmethod
+    def _host_stream(ids, doc_offsets):
+        """ids and offsets on the host, checked -> (contiguous int32 or int64 array, offsets); no device is named"""
+        import torch
         arr = np.asarray(ids)
         arr = np.ascontiguousarray(arr) if arr.dtype == np.int32 and arr.ndim == 1 else _host_array(ids)
         doc_offsets = _check_doc_offsets(doc_offsets, torch.device("cpu"), strict=True)
         if isinstance(doc_offsets, torch.Tensor):
             doc_offsets = doc_offsets.numpy()
-        return torch.from_numpy(arr).to(_cuda_device(device)), doc_offsets
+        return arr, doc_offsets
 
     def duplicate_docs(self, ids, doc_offsets, *, device=None, **kw):
         """duplicate_docs_resident() for ids on the host (a list or an array of integers; an int32 array is compared as
@@ -970,6 +992,145 @@ class Tokenizer:
         d_ids, doc_offsets = self._host_docs(ids, doc_offsets, device, kw)
         res = self.near_duplicate_docs_resident(d_ids, doc_offsets, **kw)
         return tuple(t.cpu().numpy() for t in res) if isinstance(res, tuple) else res.cpu().numpy()
+
+    # -- which documents share a window with a held-out set --------------
+    @property
+    def n_overlapping_docs(self):
+        """The number of documents with a hit that the last ngram_overlap_resident() / decontaminate_docs_resident() of
+        this tokenizer found (and their host forms); None before the first.  Read-only: it came back as a counter."""
+        return getattr(self, "_n_overlapping_docs", None)
+
+    @staticmethod
+    def _ngram_value(ngram):
+        if isinstance(ngram, bool) or not isinstance(ngram, (int, np.integer)) or not 1 <= ngram <= 64:
+            raise ValueError("ngram must be an integer from 1 to 64")
+        return int(ngram)
+
+    def ngram_index_resident(self, ref_ids, ref_doc_offsets=None, *, ngram=13):
+        """The index of a held-out set -- benchmarks, eval splits, a block list -- that ngram_overlap_resident looks a
+        corpus up in, made on the device; not in the reference.  `ref_ids` is a 1-D contiguous int32 or int64 torch
+        tensor on the GPU, `ref_doc_offsets` its n_ref_docs + 1 token positions as select_docs_resident takes them (None:
+        one document, all of ref_ids).  Every run of `ngram` consecutive ids inside one reference document is a
+        reference window; a document shorter than that contributes none.  The engine of that GPU keeps its own copy of
+        the ids and ONE index: this one replaces the one before, whose NgramIndex then raises RuntimeError when used.
+        Returns an NgramIndex (ngram, n_windows, n_distinct, device, id).  Offsets that descend or pass len(ref_ids)
+        raise ValueError.  Nothing but counters crosses PCIe."""
+        import torch
+        ngram = self._ngram_value(ngram)
+        _check_ids(ref_ids, (torch.int32, torch.int64), cuda=False)
+        dev = ref_ids.device
+        if ref_doc_offsets is None:
+            ref_doc_offsets = np.array([0, ref_ids.numel()], np.int64)
+        ref_doc_offsets = _check_doc_offsets(ref_doc_offsets, dev, strict=True)
+        _check_ids(ref_ids, (torch.int32, torch.int64))
+        roff = _place_doc_offsets(ref_doc_offsets, dev)
+        eng = engine(dev.index)
+        torch.cuda.current_stream(dev).synchronize()  # the caller's pending writes to ref_ids (and the upload above) are done
+        iid, n_windows, n_distinct = eng.ngram_index_resident(ref_ids.data_ptr(), ref_ids.element_size(), ref_ids.numel(),
+                                                              roff.data_ptr(), roff.numel() - 1, ngram)
+        return NgramIndex(ngram, n_windows, n_distinct, dev, iid)
+
+    def ngram_index(self, ref_ids, ref_doc_offsets=None, *, ngram=13, device=None):
+        """ngram_index_resident() for reference ids on the host (a list or an array of integers; an int32 array goes up
+        as int32, anything else as int64 -- the index is the same).  device: the GPU's index (default: the process-wide
+        engine's)."""
+        import torch
+        self._ngram_value(ngram)
+        arr, ref_doc_offsets = self._host_reference(ref_ids, ref_doc_offsets)
+        return self.ngram_index_resident(torch.from_numpy(arr).to(_cuda_device(device)), ref_doc_offsets, ngram=ngram)
+
+    def _host_reference(self, ref_ids, ref_doc_offsets):
+        """_host_stream of a reference, whose offsets may be None: one document"""
+        if ref_doc_offsets is None:
+            ref_doc_offsets = [0, int(np.asarray(ref_ids).size)]
+        return self._host_stream(ref_ids, ref_doc_offsets)
+
+    @staticmethod
+    def _ngram_index_on(index, dev):
+        """ValueError unless `index` (an NgramIndex: checked) was made on `dev`"""
+        if index.device != dev:
+            raise ValueError(f"the index was made on {index.device}, the ids are on {dev}")
+
+    def ngram_overlap_resident(self, index, ids, doc_offsets, *, max_len=None, keep="head", return_first=False,
+                               return_starts=False):
+        """How many windows of every document also occur in a held-out set, counted on the device: hits[d] = the
+        positions k of document d at which the index.ngram ids d[k : k + ngram] equal, by value, a window of the
+        reference `index` was made from (ngram_index_resident); not in the reference.  `ids` and `doc_offsets` are what
+        select_docs_resident takes; an int32 corpus may be looked up in an index of int64 ids and the reverse.  max_len /
+        keep: documents are cut as select_docs_resident cuts them with the same values, and a window lies inside the cut.
+        A document shorter than ngram has no window.  Exact: a hash only chooses where to look, every equality is
+        established by comparing the ids; the result does not depend on scheduling.
+
+        Returns hits, an int64 tensor [n_docs] on the device of `ids`; with return_first=True (hits, first, ref_pos):
+        first[d] the position inside the uncut document d at which its first hit starts -- it indexes what
+        token_spans_resident returns --, ref_pos[d] the lowest position of the reference at which that window starts, both
+        -1 where hits is 0; with return_starts=True also a uint8 tensor [len(ids)] that is 1 where a hit window starts.
+        n_overlapping_docs then holds the number of documents with a hit.  Offsets that descend or pass len(ids) raise
+        ValueError, an index that is no longer its engine's current one RuntimeError.  Nothing but counters crosses PCIe."""
+        import torch
+        max_len, flags = self._select_values(max_len, keep)
+        if not isinstance(index, NgramIndex):
+            raise TypeError("index must be an NgramIndex (what ngram_index_resident returns)")
+        _check_ids(ids, (torch.int32, torch.int64), cuda=False)
+        dev = ids.device
+        doc_offsets = _check_doc_offsets(doc_offsets, dev, strict=True)
+        self._ngram_index_on(index, dev)
+        _check_ids(ids, (torch.int32, torch.int64))
+        doff = _place_doc_offsets(doc_offsets, dev)
+        n_docs = doff.numel() - 1
+        hits = torch.empty(n_docs, dtype=torch.int64, device=dev)
+        first = torch.empty(n_docs, dtype=torch.int64, device=dev) if return_first else None
+        ref_pos = torch.empty(n_docs, dtype=torch.int64, device=dev) if return_first else None
+        starts = torch.empty(ids.numel(), dtype=torch.uint8, device=dev) if return_starts else None
+        eng = engine(dev.index)
+        torch.cuda.current_stream(dev).synchronize()  # the caller's pending writes to ids (and the upload above) are done
+        self._n_overlapping_docs = eng.ngram_overlap_resident(
+            index.id, ids.data_ptr(), ids.element_size(), ids.numel(), doff.data_ptr(), n_docs, max_len, flags,
+            hits.data_ptr(), first.data_ptr() if return_first else 0, ref_pos.data_ptr() if return_first else 0,
+            starts.data_ptr() if return_starts else 0)
+        res = (hits, first, ref_pos) if return_first else (hits,)
+        if return_starts:
+            res += (starts,)
+        return res if len(res) > 1 else hits
+
+    def ngram_overlap(self, index_or_ref, ids, doc_offsets, *, device=None, ngram=13, ref_doc_offsets=None, **kw):
+        """ngram_overlap_resident() for ids on the host (a list or an array of integers): NumPy hits, or the tuple.
+        index_or_ref: an NgramIndex, or the reference ids on the host, of which an index is made first (ngram,
+        ref_doc_offsets: as in ngram_index; they are not looked at when an NgramIndex comes in).  device: the GPU's
+        index (default: the process-wide engine's)."""
+        import torch
+        self._select_values(kw.get("max_len"), kw.get("keep", "head"))
+        ref = None
+        if not isinstance(index_or_ref, NgramIndex):
+            self._ngram_value(ngram)
+            ref = self._host_reference(index_or_ref, ref_doc_offsets)
+        arr, doc_offsets = self._host_stream(ids, doc_offsets)
+        dev = _cuda_device(device)
+        if ref is None:
+            self._ngram_index_on(index_or_ref, dev)
+        else:
+            index_or_ref = self.ngram_index_resident(torch.from_numpy(ref[0]).to(dev), ref[1], ngram=ngram)
+        res = self.ngram_overlap_resident(index_or_ref, torch.from_numpy(arr).to(dev), doc_offsets, **kw)
+        return tuple(t.cpu().numpy() for t in res) if isinstance(res, tuple) else res.cpu().numpy()
+
+    def decontaminate_docs_resident(self, index, ids, doc_offsets, *, min_hits=1, max_len=None, keep="head", out=None):
+        """The documents that share fewer than `min_hits` windows with a held-out set, in the order of the stream:
+        ngram_overlap_resident() and select_docs_resident() over hits < min_hits in one call.  Returns (ids',
+        doc_offsets', kept, hits): the id stream of the kept documents and its offsets as select_docs_resident returns
+        them, kept int64 [k] the kept document numbers and hits int64 [n_docs] the hits of ALL documents, all on the
+        device of `ids`.  With max_len the kept documents are cut the same way they were looked up.  out: as in
+        select_docs_resident."""
+        import torch
+        if isinstance(min_hits, bool) or not isinstance(min_hits, (int, np.integer)) or min_hits < 1:
+            raise ValueError("min_hits must be a positive integer")
+        _check_ids(ids, (torch.int32, torch.int64), cuda=False)
+        if out is not None and (not isinstance(out, torch.Tensor) or out.device != ids.device or out.dtype != ids.dtype
+                                or out.dim() != 1 or not out.is_contiguous()):
+            raise TypeError("out must be a 1-D contiguous torch tensor of the dtype and on the device of ids")
+        hits = self.ngram_overlap_resident(index, ids, doc_offsets, max_len=max_len, keep=keep)
+        kept = torch.nonzero(hits < int(min_hits)).reshape(-1)
+        res, ooff = self.select_docs_resident(ids, doc_offsets, kept, max_len=max_len, keep=keep, out=out)
+        return res, ooff, kept, hits
 
     # -- fixed-length rows from ids that live in HBM (DESIGN 4.4) ---------------------
     def rows_resident(self, ids, doc_offsets, row_len, *, stride=None, sep=None, pad=0, mode="pack", truncate="right",
