@@ -95,7 +95,11 @@ int bpe_set_stream(bpe_ctx *ctx, void *hip_stream);
  *   tile, a power of two from 64 to 65536; a tile goes through LDS 2048 positions at a time, a smaller tile whole),
  *   "ng_hash_bits" (64, 0..64: only so many bits of a window's hash choose its first table slot and its tag; 0 makes
  *   every window start at slot 0 and every probe a full comparison; an index keeps the value it was built with -- the
- *   results are the same at every value). */
+ *   results are the same at every value);
+ *   bpe_repeat_stats_resident's passes: "rp_tile" (4096: stream positions per workgroup tile, a power of two from 64
+ *   to 65536; a tile goes through LDS 2048 positions at a time, a smaller tile whole), "rp_hash_bits" (64, 0..64: only
+ *   so many bits of a window's hash choose its first table slot and its tag; 0 puts every window of a document onto one
+ *   probe chain and makes every probe a full comparison -- the results are the same at every value). */
 int bpe_set_option(bpe_ctx *ctx, const char *name, int64_t value);
 
 /* ---- input ----------------------------------------------------------------- */
@@ -668,6 +672,65 @@ int bpe_ngram_overlap_resident(bpe_ctx *ctx, uint64_t index_id, const void *d_id
                                const uint64_t *d_doc_offsets, uint64_t n_docs, uint64_t max_len, uint32_t flags,
                                int64_t *d_hits, int64_t *d_first, int64_t *d_ref_pos, uint8_t *d_starts,
                                uint64_t *n_hit_docs, uint64_t *bad_doc);
+
+/* ---- repetition statistics: repeated n-grams inside each document -------- */
+/* The repetition filters of the Gopher / MassiveText rules on an id stream in HBM: how often the windows of w = ngram
+ * consecutive ids of a document occur again inside the SAME document.  Every large buffer is ON THE DEVICE and owned by
+ * the caller.  The definition (tests/repetition_model.py is its executable form):
+ *   key(d)           the slice bpe_select_docs_resident emits for document d of ids [n], off [n_docs + 1] with the same
+ *                    max_len and flags: start s_d, length l_d
+ *   windows          a window starts at every key position k with k + w <= l_d.  A key shorter than w has no window (it
+ *                    is not shortened)
+ *   equality         two windows of the same document are equal when they hold the same ids at their full width: two
+ *                    int64 ids that differ only above bit 32 are different; negative ids are values like any other.
+ *                    Windows of different documents are never compared
+ *   repeat           position k is a repeat if an equal window starts at a lower key position of the same document
+ *   length[d]        l_d
+ *   windows[d]       max(0, l_d - w + 1)
+ *   distinct[d]      the number of distinct windows (= windows - repeats)
+ *   covered[d]       the number of key positions i that lie inside a window at a repeat: some repeat k with
+ *                    k <= i < k + w -- the token form of Gopher's "fraction inside duplicated n-grams"
+ *   top_count[d]     the largest multiplicity of any window of the document, 0 without a window
+ *   top_pos[d]       (s_d - off[d]) + the lowest start of the window with that multiplicity, among several such windows
+ *                    the one whose first start is lowest; -1 without a window: a position inside the uncut document
+ *   marks[p]         uint8 [n].  Bit 0: a repeat window starts at stream position p; bit 1: p is covered; 0 at every
+ *                    other of the n positions
+ * Exact, and the result does not depend on scheduling: a hash only chooses where to look, every equality is established
+ * by comparing ids, counts are sums, lowest starts are minima and the top window is one maximum over
+ * count << 32 | (2^32 - 1 - lowest start).
+ *   d_ids, id_width  n ids of 4 (int32) or 8 (int64) bytes, read in place, never written
+ *   d_doc_offsets    validated on the device exactly as in bpe_rows_resident: ascending, none beyond n.  The first bad
+ *                    entry goes to *bad_doc (~0 if none), the call fails with BPE_E_ARG and nothing is written
+ *   ngram            1..64
+ *   max_len, flags   as in bpe_select_docs_resident: 0 = whole documents, BPE_SELECT_TAIL = the last max_len ids
+ *   d_length .. d_top_pos  int64 [n_docs] each, each may be NULL;  d_marks: uint8 [n], may be NULL, all n bytes are
+ *                    written.  With n_docs > 0 at least one of the seven must be given
+ *   *n_repeat_docs   the documents with distinct < windows
+ * n_docs == 0 is BPE_OK with nothing written but d_marks (zeroed).
+ * BPE_E_ARG before any device work: id_width not 4 or 8, ngram outside [1, 64], an unknown flag, BPE_SELECT_TAIL with
+ * max_len == 0, d_ids = NULL with n > 0, d_doc_offsets NULL, no output with n_docs > 0, a misaligned pointer (d_ids to
+ * id_width, the others but d_marks to 8 bytes).  BPE_E_LIMIT, before anything is launched or allocated: n >= 2^32,
+ * n_docs >= 2^32 - 1.  Nothing is written to any output before the last check has passed.
+ * Passes (bpe_set_option: "rp_tile", "rp_hash_bits"), all laid out by the stream, a tile per workgroup, a lane per
+ * position: INSERT -- the ids of a tile and their halo of w - 1 in LDS; every window goes into an open-addressing table
+ * of two slots per position of [off[0], off[n_docs]), in which every key owns the slots of its own positions -- twice as
+ * many as it has windows, so that windows of different documents never meet and the probes of a tile stay as local as
+ * its ids --: a slot is claimed by atomicCAS with tag << 32 | position, a window with the same ids joins it (its own ids
+ * from LDS against the stream at the slot's position), and folds its position into the slot's lowest by atomicMin and 1
+ * into its count; READ -- the same walk after the insert pass has completed: a position
+ * that is not its slot's lowest is a repeat, the one that is speaks for its class by one 64-bit atomicMax; COVER -- the
+ * repeat marks of a tile and of the w - 1 positions before it as bits in LDS; FINISH -- the rows into the caller's
+ * columns.  Nothing is read outside [off[0], off[n_docs]).  Runs on the ctx's stream and synchronises it before
+ * returning; keeps no pointer of the caller's; only the counters {first bad entry, off[0], off[n_docs]},
+ * {n_repeat_docs} cross PCIe.
+ * Limits: the table is 16 bytes per slot, two slots per id -- 32 bytes per id --, the rows 16 bytes per document, and a call without d_marks keeps n bytes of marks of its own: a scratch group of its own,
+ * grow-only, freed with the ctx.  The call leaves the ctx's n-gram index and every other entry point's results alone. */
+int bpe_repeat_stats_resident(bpe_ctx *ctx, const void *d_ids, int32_t id_width, uint64_t n,
+                              const uint64_t *d_doc_offsets, uint64_t n_docs, uint32_t ngram,
+                              uint64_t max_len, uint32_t flags,
+                              int64_t *d_length, int64_t *d_windows, int64_t *d_distinct, int64_t *d_covered,
+                              int64_t *d_top_count, int64_t *d_top_pos, uint8_t *d_marks,
+                              uint64_t *n_repeat_docs, uint64_t *bad_doc);
 
 /* ---- measurement ------------------------------------------------------------ */
 #define BPE_PROF_WIDEN 0

@@ -118,6 +118,8 @@ _SIGS = {
                                            C.POINTER(_u64), C.POINTER(_u64)]),
     "bpe_ngram_overlap_resident": (C.c_int, [_p, _u64, _p, _i32, _u64, _p, _u64, _u64, C.c_uint32, _p, _p, _p, _p,
                                              C.POINTER(_u64), C.POINTER(_u64)]),
+    "bpe_repeat_stats_resident": (C.c_int, [_p, _p, _i32, _u64, _p, _u64, C.c_uint32, _u64, C.c_uint32, _p, _p, _p, _p,
+                                            _p, _p, _p, C.POINTER(_u64), C.POINTER(_u64)]),
     "bpe_prof_reset": (C.c_int, [_p]),
     "bpe_prof_read": (C.c_int, [_p, _p, _p, _p]),
     "bpe_encode_uses_16bit": (C.c_int, [_p, C.c_int32]),
@@ -825,6 +827,25 @@ class Engine:
             raise BadDocOffsets(int(bad_doc.value), (_lib.bpe_last_error(self._h) or b"").decode())
         self._check(rc)
         return int(nh.value)
+
+    # -- repetition statistics ---------------------------------------------------------
+    def repeat_stats_resident(self, d_ids: int, id_width: int, n: int, d_doc_off: int, n_docs: int, ngram: int = 5,
+                              max_len: int = 0, flags: int = 0, d_length: int = 0, d_windows: int = 0, d_distinct: int = 0,
+                              d_covered: int = 0, d_top_count: int = 0, d_top_pos: int = 0, d_marks: int = 0) -> int:
+        """bpe_repeat_stats_resident: d_ids (n ids of id_width = 4 or 8 bytes), d_doc_off (n_docs + 1 uint64) and, where
+        wanted (0 = not), the six columns (n_docs int64 each) and d_marks (n uint8) are device addresses.  Documents are
+        cut as select_docs_resident cuts them for the same max_len and flags.  Returns the number of documents that
+        hold a repeated window of `ngram` ids.  Offsets that descend or pass n raise BadDocOffsets(entry); nothing is
+        written then."""
+        nr, bad_doc = _u64(0), _u64(0)
+        rc = _lib.bpe_repeat_stats_resident(self._h, C.c_void_p(d_ids), id_width, n, C.c_void_p(d_doc_off), n_docs, ngram,
+                                            int(max_len), flags, C.c_void_p(d_length), C.c_void_p(d_windows),
+                                            C.c_void_p(d_distinct), C.c_void_p(d_covered), C.c_void_p(d_top_count),
+                                            C.c_void_p(d_top_pos), C.c_void_p(d_marks), C.byref(nr), C.byref(bad_doc))
+        if rc == BPE_E_ARG and bad_doc.value != 0xFFFFFFFFFFFFFFFF:
+            raise BadDocOffsets(int(bad_doc.value), (_lib.bpe_last_error(self._h) or b"").decode())
+        self._check(rc)
+        return int(nr.value)
 
     # -- measurement ----------------------------------------------------------------
     def prof_reset(self):

@@ -39,6 +39,9 @@ union ScratchWords {
               // windows} of a build, the documents with a hit of a query
         unsigned long long bad, ends[2], counts[2], hit_docs;
     } ng;
+    struct {  // bpe_repeat_stats_resident: `rows` for its offsets check, and the documents with a repeat
+        unsigned long long bad, ends[2], repeat_docs;
+    } rp;
     struct {  // encode_batch_impl (min_rank and starts: the stream-wide rounds of its longest chunks)
         unsigned long long nlong, total;
         uint32_t min_rank, pad;
@@ -378,6 +381,19 @@ struct bpe_ctx {
     int ng_tile = 4096;       // option "ng_tile": stream positions per workgroup tile of the window pass, a power of two (the fastest of
                               // 256 .. 65536 on documents of 19 ids: DESIGN 4.11)
     int ng_hash_bits = 64;    // option "ng_hash_bits": bits of the window hash that choose the first slot and the tag (tests: 0 = none)
+    // bpe_repeat_stats_resident (k_repeat.hip): a scratch of its own (grow-only) that no other entry point touches.  By
+    // the positions: the open-addressing table of the windows of one call (tag << 32 | position, the lowest position
+    // and the size of the class per slot) and the repeat marks of a call that asks for none; by the documents: repeats,
+    // covered positions and count << 32 | ~lowest start of the top window
+    DevPtr<RpSlot> d_rp_tab;
+    DevPtr<uint8_t> d_rp_marks;
+    DevPtr<uint32_t> d_rp_rep;
+    DevPtr<uint32_t> d_rp_cov;
+    DevPtr<unsigned long long> d_rp_top;
+    uint64_t cap_rp_pos = 0, cap_rp_docs = 0;
+    int rp_tile = 4096;       // option "rp_tile": stream positions per workgroup tile of the window and cover passes, a power of two
+                              // 
+    int rp_hash_bits = 64;    // option "rp_hash_bits": bits of the window hash that choose the first slot and the tag (tests: 0 = none)
     // bpe_token_spans_resident (k_spans.hip): leads | cont << 31 of every table entry, made on the device by the first
     // call after a bpe_decode_set_vocab; the second scan channel and the documents' bases (grow-only)
     DevPtr<uint32_t> d_dec_meta;

@@ -70,4 +70,5 @@
 #include "kernels/k_dupdocs.hip"
 #include "kernels/k_minhash.hip"
 #include "kernels/k_ngram.hip"
+#include "kernels/k_repeat.hip"
 #include "kernels/k_util.hip"

@@ -9,6 +9,7 @@ encoding runs on the GPU through the C-ABI in include/bpe_hip.h.  Host Python
 only does what the reference leaves to the `regex` module and to O(vocab)
 bookkeeping ("out of scope as kernels").
 """
+import collections
 import math
 import os
 import unicodedata
@@ -177,6 +178,13 @@ class NgramIndex:
     def __repr__(self):
         return (f"NgramIndex(ngram={self.ngram}, n_windows={self.n_windows}, n_distinct={self.n_distinct}, "
                 f"device={str(self.device)!r}, id={self.id})")
+
+
+class RepetitionStats(collections.namedtuple("RepetitionStats", "length windows distinct covered top_count top_pos marks")):
+    """What Tokenizer.repetition_resident returns: per document the length of the (cut) document, its windows of `ngram`
+    ids, the distinct ones, the positions inside a repeated window, the multiplicity of the most frequent window and
+    where it first starts; marks: a byte per id (bit 0: a repeat starts here, bit 1: covered), or None."""
+    __slots__ = ()
 
 
 class Tokenizer:
@@ -1131,6 +1139,148 @@ class Tokenizer:
         kept = torch.nonzero(hits < int(min_hits)).reshape(-1)
         res, ooff = self.select_docs_resident(ids, doc_offsets, kept, max_len=max_len, keep=keep, out=out)
         return res, ooff, kept, hits
+
+    # -- repeated n-grams inside each document ----------------------------
+    @property
+    def n_repetitive_docs(self):
+        """The number of documents that the last repetitive_docs_resident() / drop_repetitive_docs_resident() of this
+        tokenizer flagged; None before the first."""
+        return getattr(self, "_n_repetitive_docs", None)
+
+    @staticmethod
+    def _repetition_rules(top, dup):
+        """the rule lists of repetitive_docs_resident -> ((w, t), ...) twice, checked; ValueError for anything else"""
+        out = []
+        for name, rules in (("top", top), ("dup", dup)):
+            try:
+                rules = tuple(tuple(r) for r in rules)
+            except TypeError:
+                raise ValueError(f"{name} must be a sequence of (ngram, threshold) pairs") from None
+            for r in rules:
+                if len(r) != 2:
+                    raise ValueError(f"{name} must be a sequence of (ngram, threshold) pairs")
+                w, t = r
+                if isinstance(w, bool) or not isinstance(w, (int, np.integer)) or not 1 <= w <= 64:
+                    raise ValueError(f"{name}: an ngram must be an integer from 1 to 64")
+                if isinstance(t, bool) or not isinstance(t, (int, float, np.integer, np.floating)) or not t >= 0 \
+                        or t == float("inf"):
+                    raise ValueError(f"{name}: a threshold must be a real number >= 0")
+            out.append(tuple((int(w), float(t)) for w, t in rules))
+        if not out[0] and not out[1]:
+            raise ValueError("top and dup are both empty: no rule")
+        return out[0], out[1]
+
+    @staticmethod
+    def _repetition_flags(stats, top, dup):
+        """the rule of repetitive_docs_resident on stats = {w: RepetitionStats}: bool [n_docs], both sides in float64"""
+        import torch
+        length = next(iter(stats.values())).length
+        flagged = torch.zeros(length.numel(), dtype=torch.bool, device=length.device)
+        flen = length.to(torch.float64)
+        for rules, column in ((top, "top_count"), (dup, "covered")):
+            for w, t in rules:
+                lhs = getattr(stats[w], column)
+                lhs = (lhs * w if column == "top_count" else lhs).to(torch.float64)
+                flagged |= lhs > t * flen
+        flagged &= length > 0
+        return flagged
+
+    def repetition_resident(self, ids, doc_offsets, *, ngram=5, max_len=None, keep="head", return_marks=False):
+        """How much of every document repeats itself, counted on the device: the statistics of the windows of `ngram`
+        consecutive ids of each document that occur more than once inside that SAME document -- what the repetition
+        filters of the Gopher / MassiveText rules are made of; not in the reference.  `ids` and `doc_offsets` are what
+        select_docs_resident takes.  max_len / keep: documents are cut as select_docs_resident cuts them with the same
+        values, and a window lies inside the cut; a document shorter than ngram has no window.  A window that equals
+        one starting earlier in the document is a repeat.  Exact: a hash only chooses where to look, every equality is
+        established by comparing the ids at their full width; the result does not depend on scheduling.
+
+        Returns a RepetitionStats of int64 tensors [n_docs] on the device of `ids`: length (of the cut document), windows,
+        distinct (windows - repeats), covered (the positions that lie inside a window at a repeat), top_count (the
+        largest multiplicity of a window, 0 without one), top_pos (where in the uncut document the lowest window of
+        that multiplicity starts, -1 without one); marks is None, or with return_marks=True a uint8 tensor [len(ids)]:
+        bit 0 where a repeat starts, bit 1 where the position is covered.  Offsets that descend or pass len(ids) raise
+        ValueError.  Nothing but counters crosses PCIe."""
+        return self._repetition(ids, doc_offsets, ngram, max_len, keep, return_marks)[0]
+
+    def _repetition(self, ids, doc_offsets, ngram, max_len, keep, return_marks, columns=None, doff=None):
+        """(RepetitionStats, n_repeat_docs, the offsets on the device); columns: the fields wanted (None: all)"""
+        import torch
+        ngram = self._ngram_value(ngram)
+        max_len, flags = self._select_values(max_len, keep)
+        _check_ids(ids, (torch.int32, torch.int64), cuda=False)
+        dev = ids.device
+        if doff is None:
+            doc_offsets = _check_doc_offsets(doc_offsets, dev, strict=True)
+        _check_ids(ids, (torch.int32, torch.int64))
+        if doff is None:
+            doff = _place_doc_offsets(doc_offsets, dev)
+        n_docs = doff.numel() - 1
+        names = RepetitionStats._fields[:6]
+        cols = {name: torch.empty(n_docs, dtype=torch.int64, device=dev) if columns is None or name in columns else None
+                for name in names}
+        marks = torch.empty(ids.numel(), dtype=torch.uint8, device=dev) if return_marks else None
+        eng = engine(dev.index)
+        torch.cuda.current_stream(dev).synchronize()  # the caller's pending writes to ids (and the upload above) are done
+        n_rep = eng.repeat_stats_resident(ids.data_ptr(), ids.element_size(), ids.numel(), doff.data_ptr(), n_docs, ngram,
+                                          max_len, flags, *[0 if cols[name] is None else cols[name].data_ptr() for name in names],
+                                          marks.data_ptr() if return_marks else 0)
+        return RepetitionStats(*[cols[name] for name in names], marks), n_rep, doff
+
+    def repetition(self, ids, doc_offsets, *, device=None, ngram=5, **kw):
+        """repetition_resident() for ids on the host (a list or an array of integers; an int32 array goes up as int32,
+        anything else as int64): a RepetitionStats of NumPy arrays.  device: the GPU's index (default: the process-wide
+        engine's)."""
+        self._ngram_value(ngram)
+        d_ids, doc_offsets = self._host_docs(ids, doc_offsets, device, kw)
+        res = self.repetition_resident(d_ids, doc_offsets, ngram=ngram, **kw)
+        return RepetitionStats(*[None if t is None else t.cpu().numpy() for t in res])
+
+    def repetitive_docs_resident(self, ids, doc_offsets, *, top=((2, .20), (3, .18), (4, .16)),
+                                 dup=((5, .15), (6, .14), (7, .13), (8, .12), (9, .11), (10, .10)), max_len=None,
+                                 keep="head"):
+        """The documents the repetition filters of the Gopher / MassiveText rules drop, found on the device: flagged, a
+        bool tensor [n_docs] on the device of `ids`.  A document is flagged if for some (w, t) of `top` its most
+        frequent window of w ids makes up more than t of it -- top_count_w * w > t * length -- or if for some (w, t) of
+        `dup` more than t of it lies inside repeated windows of w ids -- covered_w > t * length --, the columns those of
+        repetition_resident(ngram=w), both sides compared in float64.  The defaults are Gopher's thresholds.  A document
+        of length 0 is never flagged.  One engine call per distinct w.  n_repetitive_docs then holds the number of
+        flagged documents."""
+        import torch
+        top, dup = self._repetition_rules(top, dup)
+        self._select_values(max_len, keep)
+        _check_ids(ids, (torch.int32, torch.int64), cuda=False)
+        doc_offsets = _check_doc_offsets(doc_offsets, ids.device, strict=True)
+        _check_ids(ids, (torch.int32, torch.int64))
+        want = {}
+        for rules, column in ((top, "top_count"), (dup, "covered")):
+            for w, _ in rules:
+                want.setdefault(w, {"length"}).add(column)
+        stats, doff = {}, None
+        for w in sorted(want):
+            stats[w], _, doff = self._repetition(ids, doc_offsets, w, max_len, keep, False, columns=want[w], doff=doff)
+        flagged = self._repetition_flags(stats, top, dup)
+        self._n_repetitive_docs = int(flagged.sum().item())
+        return flagged
+
+    def drop_repetitive_docs_resident(self, ids, doc_offsets, *, top=((2, .20), (3, .18), (4, .16)),
+                                      dup=((5, .15), (6, .14), (7, .13), (8, .12), (9, .11), (10, .10)), max_len=None,
+                                      keep="head", out=None):
+        """The documents that repetitive_docs_resident() does not flag, in the order of the stream: that call and
+        select_docs_resident() in one.  Returns (ids', doc_offsets', kept, flagged): the id stream of the kept
+        documents and its offsets as select_docs_resident returns them, kept int64 [k] the kept document numbers and
+        flagged bool [n_docs] the flags of ALL documents, all on the device of `ids`.  With max_len the kept documents
+        are cut the same way they were judged.  out: as in select_docs_resident."""
+        import torch
+        self._repetition_rules(top, dup)
+        self._select_values(max_len, keep)
+        _check_ids(ids, (torch.int32, torch.int64), cuda=False)
+        if out is not None and (not isinstance(out, torch.Tensor) or out.device != ids.device or out.dtype != ids.dtype
+                                or out.dim() != 1 or not out.is_contiguous()):
+            raise TypeError("out must be a 1-D contiguous torch tensor of the dtype and on the device of ids")
+        flagged = self.repetitive_docs_resident(ids, doc_offsets, top=top, dup=dup, max_len=max_len, keep=keep)
+        kept = torch.nonzero(~flagged).reshape(-1)
+        res, ooff = self.select_docs_resident(ids, doc_offsets, kept, max_len=max_len, keep=keep, out=out)
+        return res, ooff, kept, flagged
 
     # -- fixed-length rows from ids that live in HBM (DESIGN 4.4) ---------------------
     def rows_resident(self, ids, doc_offsets, row_len, *, stride=None, sep=None, pad=0, mode="pack", truncate="right",
