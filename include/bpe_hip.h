@@ -99,7 +99,11 @@ int bpe_set_stream(bpe_ctx *ctx, void *hip_stream);
  *   bpe_repeat_stats_resident's passes: "rp_tile" (4096: stream positions per workgroup tile, a power of two from 64
  *   to 65536; a tile goes through LDS 2048 positions at a time, a smaller tile whole), "rp_hash_bits" (64, 0..64: only
  *   so many bits of a window's hash choose its first table slot and its tag; 0 puts every window of a document onto one
- *   probe chain and makes every probe a full comparison -- the results are the same at every value). */
+ *   probe chain and makes every probe a full comparison -- the results are the same at every value);
+ *   bpe_dup_spans_resident's passes: "ds_tile" (4096: stream positions per workgroup tile, a power of two from 64 to
+ *   65536; a tile goes through LDS 2048 positions at a time, a smaller tile whole), "ds_hash_bits" (64, 0..64: only so
+ *   many bits of a window's hash choose its first table slot and its tag; 0 puts every window of the stream onto one
+ *   probe chain with tag 0 and makes every probe a full comparison -- the results are the same at every value). */
 int bpe_set_option(bpe_ctx *ctx, const char *name, int64_t value);
 
 /* ---- input ----------------------------------------------------------------- */
@@ -731,6 +735,99 @@ int bpe_repeat_stats_resident(bpe_ctx *ctx, const void *d_ids, int32_t id_width,
                               int64_t *d_length, int64_t *d_windows, int64_t *d_distinct, int64_t *d_covered,
                               int64_t *d_top_count, int64_t *d_top_pos, uint8_t *d_marks,
                               uint64_t *n_repeat_docs, uint64_t *bad_doc);
+
+/* ---- span de-duplication: windows an earlier document already holds -------- */
+/* The exact-substring de-duplication of Lee et al. ("Deduplicating training data makes language models better") and the
+ * span removal of RefinedWeb on an id stream in HBM: which windows of w = ngram consecutive ids of a document were already
+ * seen in an EARLIER document of the same stream -- the licence text, the menu, the signature that otherwise different
+ * documents share.  Every large buffer is ON THE DEVICE and owned by the caller.  The definition
+ * (tests/dupspans_model.py is its executable form):
+ *   key(d)           the slice bpe_select_docs_resident emits for document d of ids [n], off [n_docs + 1] with the same
+ *                    max_len and BPE_SELECT_TAIL: start s_d (an absolute stream position), length l_d
+ *   windows          a window starts at every absolute position p with s_d <= p and p + w <= s_d + l_d.  A key shorter
+ *                    than w has none
+ *   equality         two windows are equal when they hold the same ids at their full width: two int64 ids that differ
+ *                    only above bit 32 differ; negative ids are values like any other.  Windows of ALL documents are
+ *                    compared with one another
+ *   low(W)           the lowest absolute position at which a window equal to W starts, over all keys
+ *   seen             the window at p in document d is seen if low(W) < s_d: an equal window starts inside an earlier
+ *                    document's key (the default scope).  With BPE_SPANS_ANYWHERE it is seen if low(W) < p: every
+ *                    occurrence but the stream's first, in-document repeats included -- Lee et al.'s rule
+ *   length[d]        l_d
+ *   windows[d]       max(0, l_d - w + 1)
+ *   seen[d]          the number of seen positions
+ *   covered[d]       the key positions i with k <= i < k + w for some seen k
+ *   first[d]         (s_d - off[d]) + the lowest seen position relative to s_d, -1 without one: a position inside the
+ *                    uncut document, like bpe_ngram_overlap_resident's first
+ *   src_pos[d]       low(W) of the window at that first seen position, -1 without one: an absolute stream position;
+ *                    upper_bound(off, src_pos) - 1 names the source document
+ *   marks[p]         uint8 [n].  Bit 0: a seen window starts at stream position p; bit 1: p is covered; 0 at every other
+ *                    of the n positions
+ * Exact, and the result does not depend on scheduling: a hash only chooses where to look, every equality is established
+ * by comparing ids, counts are sums, low, first and src_pos are minima -- first << 32 | low goes through one 64-bit
+ * atomicMin, and equal windows share one low.
+ *   d_ids, id_width  n ids of 4 (int32) or 8 (int64) bytes, read in place, never written
+ *   d_doc_offsets    validated on the device exactly as in bpe_rows_resident: ascending, none beyond n.  The first bad
+ *                    entry goes to *bad_doc (~0 if none), the call fails with BPE_E_ARG and nothing is written
+ *   ngram            1..64
+ *   max_len, flags   as in bpe_select_docs_resident: 0 = whole documents, BPE_SELECT_TAIL = the last max_len ids;
+ *                    BPE_SPANS_ANYWHERE = the scope above
+ *   d_length .. d_src_pos  int64 [n_docs] each, each may be NULL;  d_marks: uint8 [n], may be NULL, all n bytes are
+ *                    written.  With n_docs > 0 at least one of the seven must be given
+ *   *n_docs_seen     the documents with seen > 0;  *n_windows: all windows;  *n_distinct: the distinct ones (each may be
+ *                    NULL).  With BPE_SPANS_ANYWHERE the seen windows sum to n_windows - n_distinct
+ * n_docs == 0 is BPE_OK with nothing written but d_marks (zeroed).
+ * BPE_E_ARG before any device work: id_width not 4 or 8, ngram outside [1, 64], an unknown flag, BPE_SELECT_TAIL with
+ * max_len == 0, d_ids = NULL with n > 0, d_doc_offsets NULL, no output with n_docs > 0, a misaligned pointer (d_ids to
+ * id_width, the others but d_marks to 8 bytes).  BPE_E_LIMIT, before anything is launched or allocated: n >= 2^32,
+ * n_docs >= 2^32 - 1.  Nothing is written to any output before the last check has passed.
+ * Passes (bpe_set_option: "ds_tile", "ds_hash_bits"), all laid out by the stream, a tile per workgroup, a lane per
+ * position: BUILD -- the ids of a tile and their halo of w - 1 in LDS; every window goes into ONE open-addressing table
+ * of 2 positions + 1 slots over [off[0], off[n_docs]): a slot is claimed by atomicCAS with tag << 32 | position, a window
+ * with the same ids joins it (its own ids from LDS against the stream at the slot's position: no copy of the stream is
+ * made), and folds its position into the slot's lowest by atomicMin; QUERY -- the same walk after the build has
+ * completed: every window finds the slot of its class, reads its lowest and applies the scope rule; COVER -- the cover
+ * pass of bpe_repeat_stats_resident, unchanged, over this call's marks; FINISH -- the rows into the caller's columns.
+ * Every probe loop carries its bound; a window the query does not find is counted and the call returns BPE_E_INTERNAL.
+ * A stream none of whose positions can hold a window skips the passes.  Nothing is read outside [off[0], off[n_docs]).
+ * Runs on the ctx's stream and synchronises it before returning; keeps no pointer of the caller's; only the counters
+ * {first bad entry, off[0], off[n_docs]}, {n_windows, n_distinct, windows not found, n_docs_seen} cross PCIe.
+ * Limits: the table is 16 bytes per slot, two slots per id -- 32 bytes per id --, the rows 16 bytes per document, and a
+ * call without d_marks keeps n bytes of marks of its own: a scratch group of its own, grow-only, freed with the ctx.
+ * The seen set lives for one call: a corpus larger than one stream needs an index with a lifetime like
+ * bpe_ngram_index_resident's.  The call leaves the ctx's n-gram index, the repetition scratch and every other entry
+ * point's results alone. */
+#define BPE_SPANS_ANYWHERE 2u
+int bpe_dup_spans_resident(bpe_ctx *ctx, const void *d_ids, int32_t id_width, uint64_t n,
+                           const uint64_t *d_doc_offsets, uint64_t n_docs, uint32_t ngram,
+                           uint64_t max_len, uint32_t flags,
+                           int64_t *d_length, int64_t *d_windows, int64_t *d_seen, int64_t *d_covered,
+                           int64_t *d_first, int64_t *d_src_pos, uint8_t *d_marks,
+                           uint64_t *n_docs_seen, uint64_t *n_windows, uint64_t *n_distinct, uint64_t *bad_doc);
+
+/* Cut marked ids out of a stream on the device: what the marks of bpe_dup_spans_resident and
+ * bpe_repeat_stats_resident and the starts of bpe_ngram_overlap_resident are for (tests/dupspans_model.py: keep).
+ *   kept             position p of [off[0], off[n_docs]) is kept iff (mask[p] & bits) != 0; with BPE_KEEP_DROP iff
+ *                    (mask[p] & bits) == 0.  Ids outside that range are dropped
+ *   out              the kept ids in order, in the width of d_ids
+ *   out_offsets[d]   the number of kept positions in [off[0], off[d]), d = 0 .. n_docs: a document that loses everything
+ *                    stays as an empty document, and document numbers do not change
+ *   d_mask           uint8 [n], read inside [off[0], off[n_docs]) only;  bits: 1..255
+ *   d_out, out_cap   d_out = NULL or out_cap = 0: a count-only call (*n_out and d_out_offsets are written all the same).
+ *                    out_cap < total fails with BPE_E_CAP, *n_out set, d_out untouched
+ *   d_out_offsets    n_docs + 1 words, never NULL
+ * BPE_E_ARG before any device work: id_width not 4 or 8, bits outside [1, 255], an unknown flag, a NULL pointer but
+ * d_out (d_ids and d_mask with n > 0), a misaligned pointer, d_out [out_cap] overlapping d_ids [n].  BPE_E_LIMIT: n >= 2^32.
+ * Offsets are validated as in bpe_rows_resident (*bad_doc, BPE_E_ARG, nothing written).  A length pass (0 or 1 per
+ * position), a scan and a placement pass by the skeleton bpe_project_resident and bpe_select_docs_resident share: it
+ * uses the decode scratch (12 bytes per id) and drops a pending bpe_decode_batch result, as bpe_select_docs_resident
+ * does.  Runs on the ctx's stream and synchronises it; only counters cross PCIe. */
+#define BPE_KEEP_DROP 1u
+int bpe_keep_ids_resident(bpe_ctx *ctx, const void *d_ids, int32_t id_width, uint64_t n,
+                          const uint64_t *d_doc_offsets, uint64_t n_docs,
+                          const uint8_t *d_mask, uint32_t bits, uint32_t flags,
+                          void *d_out, uint64_t out_cap, uint64_t *d_out_offsets,
+                          uint64_t *n_out, uint64_t *bad_doc);
 
 /* ---- measurement ------------------------------------------------------------ */
 #define BPE_PROF_WIDEN 0

@@ -120,6 +120,10 @@ _SIGS = {
                                              C.POINTER(_u64), C.POINTER(_u64)]),
     "bpe_repeat_stats_resident": (C.c_int, [_p, _p, _i32, _u64, _p, _u64, C.c_uint32, _u64, C.c_uint32, _p, _p, _p, _p,
                                             _p, _p, _p, C.POINTER(_u64), C.POINTER(_u64)]),
+    "bpe_dup_spans_resident": (C.c_int, [_p, _p, _i32, _u64, _p, _u64, C.c_uint32, _u64, C.c_uint32, _p, _p, _p, _p,
+                                         _p, _p, _p, C.POINTER(_u64), C.POINTER(_u64), C.POINTER(_u64), C.POINTER(_u64)]),
+    "bpe_keep_ids_resident": (C.c_int, [_p, _p, _i32, _u64, _p, _u64, _p, C.c_uint32, C.c_uint32, _p, _u64, _p,
+                                        C.POINTER(_u64), C.POINTER(_u64)]),
     "bpe_prof_reset": (C.c_int, [_p]),
     "bpe_prof_read": (C.c_int, [_p, _p, _p, _p]),
     "bpe_encode_uses_16bit": (C.c_int, [_p, C.c_int32]),
@@ -316,6 +320,8 @@ class BadPair(IndexError):
 ROWS_PACK, ROWS_PER_DOC = 0, 1
 ROWS_HAS_SEP, ROWS_TRUNC_LEFT, ROWS_PAD_LEFT = 1, 2, 4
 SELECT_TAIL = 1
+SPANS_ANYWHERE = 2
+KEEP_DROP = 1
 
 
 def _ptr(a):
@@ -846,6 +852,45 @@ class Engine:
             raise BadDocOffsets(int(bad_doc.value), (_lib.bpe_last_error(self._h) or b"").decode())
         self._check(rc)
         return int(nr.value)
+
+    # -- span de-duplication -----------------------------------------------------------
+    def dup_spans_resident(self, d_ids: int, id_width: int, n: int, d_doc_off: int, n_docs: int, ngram: int = 50,
+                           max_len: int = 0, flags: int = 0, d_length: int = 0, d_windows: int = 0, d_seen: int = 0,
+                           d_covered: int = 0, d_first: int = 0, d_src_pos: int = 0, d_marks: int = 0):
+        """bpe_dup_spans_resident: d_ids (n ids of id_width = 4 or 8 bytes), d_doc_off (n_docs + 1 uint64) and, where
+        wanted (0 = not), the six columns (n_docs int64 each) and d_marks (n uint8) are device addresses.  Documents are
+        cut as select_docs_resident cuts them for the same max_len and flags; flags SPANS_ANYWHERE = a window is seen
+        if it starts anywhere earlier in the stream, not only in an earlier document.  Returns (documents with a seen
+        window, windows, distinct windows).  Offsets that descend or pass n raise BadDocOffsets(entry); nothing is
+        written then."""
+        ns, nw, nd, bad_doc = _u64(0), _u64(0), _u64(0), _u64(0)
+        rc = _lib.bpe_dup_spans_resident(self._h, C.c_void_p(d_ids), id_width, n, C.c_void_p(d_doc_off), n_docs, ngram,
+                                         int(max_len), flags, C.c_void_p(d_length), C.c_void_p(d_windows),
+                                         C.c_void_p(d_seen), C.c_void_p(d_covered), C.c_void_p(d_first),
+                                         C.c_void_p(d_src_pos), C.c_void_p(d_marks), C.byref(ns), C.byref(nw),
+                                         C.byref(nd), C.byref(bad_doc))
+        if rc == BPE_E_ARG and bad_doc.value != 0xFFFFFFFFFFFFFFFF:
+            raise BadDocOffsets(int(bad_doc.value), (_lib.bpe_last_error(self._h) or b"").decode())
+        self._check(rc)
+        return int(ns.value), int(nw.value), int(nd.value)
+
+    def keep_ids_resident(self, d_ids: int, id_width: int, n: int, d_doc_off: int, n_docs: int, d_mask: int,
+                          bits: int = 0xFF, flags: int = 0, d_out: int = 0, out_cap: int = 0, d_ooff: int = 0) -> int:
+        """bpe_keep_ids_resident: d_ids (n ids of id_width = 4 or 8 bytes), d_doc_off (n_docs + 1 uint64), d_mask (n
+        uint8), d_out (room for out_cap ids of the same width; 0 = only count) and d_ooff (n_docs + 1 uint64, always
+        written when the call counts) are device addresses.  A position inside the documents is kept iff mask & bits is
+        not 0, with flags KEEP_DROP iff it is 0.  Returns the number of ids kept.  Offsets that descend or pass n raise
+        BadDocOffsets(entry); too little room raises OutputTooSmall."""
+        no, bad_doc = _u64(0), _u64(0)
+        rc = _lib.bpe_keep_ids_resident(self._h, C.c_void_p(d_ids), id_width, n, C.c_void_p(d_doc_off), n_docs,
+                                        C.c_void_p(d_mask), bits, flags, C.c_void_p(d_out), out_cap, C.c_void_p(d_ooff),
+                                        C.byref(no), C.byref(bad_doc))
+        if rc == BPE_E_ARG and bad_doc.value != 0xFFFFFFFFFFFFFFFF:
+            raise BadDocOffsets(int(bad_doc.value), (_lib.bpe_last_error(self._h) or b"").decode())
+        if rc == BPE_E_CAP:
+            raise OutputTooSmall(int(no.value), (_lib.bpe_last_error(self._h) or b"").decode())
+        self._check(rc)
+        return int(no.value)
 
     # -- measurement ----------------------------------------------------------------
     def prof_reset(self):

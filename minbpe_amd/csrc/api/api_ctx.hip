@@ -42,6 +42,10 @@ union ScratchWords {
     struct {  // bpe_repeat_stats_resident: `rows` for its offsets check, and the documents with a repeat
         unsigned long long bad, ends[2], repeat_docs;
     } rp;
+    struct {  // bpe_dup_spans_resident: `rows` for its offsets check, {windows, distinct windows, windows the query did
+              // not find}, and the documents with a seen window (the last four read back as one block)
+        unsigned long long bad, ends[2], counts[3], seen_docs;
+    } ds;
     struct {  // encode_batch_impl (min_rank and starts: the stream-wide rounds of its longest chunks)
         unsigned long long nlong, total;
         uint32_t min_rank, pad;
@@ -394,6 +398,19 @@ struct bpe_ctx {
     int rp_tile = 4096;       // option "rp_tile": stream positions per workgroup tile of the window and cover passes, a power of two
                               // 
     int rp_hash_bits = 64;    // option "rp_hash_bits": bits of the window hash that choose the first slot and the tag (tests: 0 = none)
+    // bpe_dup_spans_resident (k_dupspans.hip): a scratch of its own (grow-only) that no other entry point touches.  By
+    // the positions: the open-addressing table of the windows of one call (tag << 32 | position and the lowest
+    // position of the class per slot) and the marks of a call that asks for none; by the documents: seen windows,
+    // covered positions and first << 32 | low of the first seen window
+    DevPtr<DsSlot> d_ds_tab;
+    DevPtr<uint8_t> d_ds_marks;
+    DevPtr<uint32_t> d_ds_seen;
+    DevPtr<uint32_t> d_ds_cov;
+    DevPtr<unsigned long long> d_ds_min;
+    uint64_t cap_ds_pos = 0, cap_ds_docs = 0;
+    int ds_tile = 4096;       // option "ds_tile": stream positions per workgroup tile of the window and cover passes, a power of two
+                              // 
+    int ds_hash_bits = 64;    // option "ds_hash_bits": bits of the window hash that choose the first slot and the tag (tests: 0 = none)
     // bpe_token_spans_resident (k_spans.hip): leads | cont << 31 of every table entry, made on the device by the first
     // call after a bpe_decode_set_vocab; the second scan channel and the documents' bases (grow-only)
     DevPtr<uint32_t> d_dec_meta;

@@ -101,7 +101,8 @@ const OptRow OPTIONS[] = {
 // rows, looked up after it.  The id histogram (bpe_count_resident): bins, ids; document selection
 // (bpe_select_docs_resident): elements, output starts; document de-duplication (bpe_dup_docs_resident): positions, ids, bits;
 // MinHash signatures (bpe_minhash_resident): positions; n-gram overlap (bpe_ngram_index_resident,
-// bpe_ngram_overlap_resident): positions, bits; repetition statistics (bpe_repeat_stats_resident): positions, bits
+// bpe_ngram_overlap_resident): positions, bits; repetition statistics (bpe_repeat_stats_resident): positions, bits; span
+// de-duplication (bpe_dup_spans_resident): positions, bits
 const OptRow OPTIONS_MORE[] = {
     OPT_STEP(count_lds_bins, 256, COUNT_LDS_BINS_MAX, 256),
     OPT(count_flush, 64, 1ll << 31),
@@ -116,6 +117,8 @@ const OptRow OPTIONS_MORE[] = {
     OPT(ng_hash_bits, 0, 64),
     OPT_NAMED("rp_tile", rp_tile, OPT_POW2, 64, RP_TILE_MAX, 1),
     OPT(rp_hash_bits, 0, 64),
+    OPT_NAMED("ds_tile", ds_tile, OPT_POW2, 64, DS_TILE_MAX, 1),
+    OPT(ds_hash_bits, 0, 64),
 };
 
 #undef OPT_RAW

@@ -71,4 +71,6 @@
 #include "kernels/k_minhash.hip"
 #include "kernels/k_ngram.hip"
 #include "kernels/k_repeat.hip"
+#include "kernels/k_dupspans.hip"
+#include "kernels/k_keep.hip"
 #include "kernels/k_util.hip"

@@ -187,6 +187,14 @@ class RepetitionStats(collections.namedtuple("RepetitionStats", "length windows 
     __slots__ = ()
 
 
+class SpanDupStats(collections.namedtuple("SpanDupStats", "length windows seen covered first src_pos marks")):
+    """What Tokenizer.duplicate_spans_resident returns: per document the length of the (cut) document, its windows of
+    `ngram` ids, those of them already seen earlier in the stream, the positions inside a seen window, where in the uncut
+    document the first seen window starts and the stream position at which its ids first stand (-1 without one); marks: a
+    byte per id (bit 0: a seen window starts here, bit 1: covered), or None."""
+    __slots__ = ()
+
+
 class Tokenizer:
     """Base class: state, vocab construction, save/load (base.py:66-165)."""
 
@@ -1281,6 +1289,171 @@ class Tokenizer:
         kept = torch.nonzero(~flagged).reshape(-1)
         res, ooff = self.select_docs_resident(ids, doc_offsets, kept, max_len=max_len, keep=keep, out=out)
         return res, ooff, kept, flagged
+
+    # -- windows an earlier document already holds ------------------------
+    @property
+    def n_docs_with_duplicate_spans(self):
+        """The number of documents with a seen window that the last duplicate_spans_resident() /
+        drop_duplicate_spans_resident() of this tokenizer found (and their host forms); None before the first."""
+        return getattr(self, "_n_docs_with_duplicate_spans", None)
+
+    @property
+    def n_span_windows(self):
+        """The windows of all documents in that call, repeats counted; None before the first."""
+        return getattr(self, "_n_span_windows", None)
+
+    @property
+    def n_distinct_span_windows(self):
+        """The distinct windows of all documents in that call; None before the first."""
+        return getattr(self, "_n_distinct_span_windows", None)
+
+    @staticmethod
+    def _scope_value(scope):
+        """the library's flag of a scope; ValueError for a scope it does not know"""
+        if not isinstance(scope, str) or scope not in ("earlier_doc", "anywhere"):
+            raise ValueError(f"scope={scope!r} not understood: 'earlier_doc' or 'anywhere'")
+        return _native.SPANS_ANYWHERE if scope == "anywhere" else 0
+
+    @staticmethod
+    def _check_out(out, ids):
+        """TypeError unless `out` is None or a tensor that select_docs_resident would take for `ids`"""
+        import torch
+        if out is not None and (not isinstance(out, torch.Tensor) or out.device != ids.device or out.dtype != ids.dtype
+                                or out.dim() != 1 or not out.is_contiguous()):
+            raise TypeError("out must be a 1-D contiguous torch tensor of the dtype and on the device of ids")
+
+    def duplicate_spans_resident(self, ids, doc_offsets, *, ngram=50, scope="earlier_doc", max_len=None, keep="head",
+                                 return_marks=False):
+        """Which stretches of every document were already seen in an EARLIER document of the same stream, found on the
+        device: the licence text, the menu, the signature that otherwise different documents share -- the
+        exact-substring de-duplication of Lee et al. (windows of 50 tokens) and RefinedWeb's span removal; not in the
+        reference.  `ids` and `doc_offsets` are what select_docs_resident takes.  max_len / keep: documents are cut as
+        select_docs_resident cuts them with the same values, and a window lies inside the cut; a document shorter than
+        ngram has no window.  The windows of ALL documents are compared with one another; a window is seen if an equal
+        one starts inside an earlier document (scope="earlier_doc"), or anywhere earlier in the stream, in-document
+        repeats included (scope="anywhere": every occurrence but the first).  Exact: a hash only chooses where to look,
+        every equality is established by comparing the ids at their full width; the result does not depend on scheduling.
+
+        Returns a SpanDupStats of int64 tensors [n_docs] on the device of `ids`: length (of the cut document), windows,
+        seen, covered (the positions that lie inside a seen window), first (where in the uncut document the first seen
+        window starts, -1 without one), src_pos (the stream position at which that window's ids first stand, -1;
+        searchsorted(doc_offsets, src_pos, right=True) - 1 is the source document); marks is None, or with
+        return_marks=True a uint8 tensor [len(ids)]: bit 0 where a seen window starts, bit 1 where the position is covered
+        -- what keep_ids_resident(bits=2, drop=True) cuts out.  n_docs_with_duplicate_spans, n_span_windows and
+        n_distinct_span_windows then hold the counters.  Offsets that descend or pass len(ids) raise ValueError.  Nothing
+        but counters crosses PCIe."""
+        return self._duplicate_spans(ids, doc_offsets, ngram, scope, max_len, keep, return_marks)[0]
+
+    def _duplicate_spans(self, ids, doc_offsets, ngram, scope, max_len, keep, return_marks):
+        """(SpanDupStats, the offsets on the device)"""
+        import torch
+        ngram = self._ngram_value(ngram)
+        flags = self._scope_value(scope)
+        max_len, tail = self._select_values(max_len, keep)
+        _check_ids(ids, (torch.int32, torch.int64), cuda=False)
+        dev = ids.device
+        doc_offsets = _check_doc_offsets(doc_offsets, dev, strict=True)
+        _check_ids(ids, (torch.int32, torch.int64))
+        doff = _place_doc_offsets(doc_offsets, dev)
+        n_docs = doff.numel() - 1
+        cols = [torch.empty(n_docs, dtype=torch.int64, device=dev) for _ in range(6)]
+        marks = torch.empty(ids.numel(), dtype=torch.uint8, device=dev) if return_marks else None
+        eng = engine(dev.index)
+        torch.cuda.current_stream(dev).synchronize()  # the caller's pending writes to ids (and the upload above) are done
+        counters = eng.dup_spans_resident(ids.data_ptr(), ids.element_size(), ids.numel(), doff.data_ptr(), n_docs, ngram,
+                                          max_len, flags | tail, *[col.data_ptr() for col in cols],
+                                          marks.data_ptr() if return_marks else 0)
+        self._n_docs_with_duplicate_spans, self._n_span_windows, self._n_distinct_span_windows = counters
+        return SpanDupStats(*cols, marks), doff
+
+    def duplicate_spans(self, ids, doc_offsets, *, device=None, ngram=50, scope="earlier_doc", **kw):
+        """duplicate_spans_resident() for ids on the host (a list or an array of integers; an int32 array goes up as
+        int32, anything else as int64): a SpanDupStats of NumPy arrays.  device: the GPU's index (default: the
+        process-wide engine's)."""
+        self._ngram_value(ngram)
+        self._scope_value(scope)
+        d_ids, doc_offsets = self._host_docs(ids, doc_offsets, device, kw)
+        res = self.duplicate_spans_resident(d_ids, doc_offsets, ngram=ngram, scope=scope, **kw)
+        return SpanDupStats(*[None if t is None else t.cpu().numpy() for t in res])
+
+    @staticmethod
+    def _keep_values(bits, drop):
+        """(bits, flags) of the library from the keywords; ValueError for values it does not know"""
+        if isinstance(bits, bool) or not isinstance(bits, (int, np.integer)) or not 1 <= bits <= 255:
+            raise ValueError("bits must be an integer from 1 to 255")
+        if not isinstance(drop, (bool, np.bool_)):
+            raise ValueError("drop must be True or False")
+        return int(bits), _native.KEEP_DROP if drop else 0
+
+    def keep_ids_resident(self, ids, doc_offsets, mask, *, bits=0xFF, drop=False, out=None):
+        """The ids at the marked positions of every document, cut out of the stream on the device -- or, with drop=True,
+        the ids at the unmarked ones; not in the reference.  `ids` and `doc_offsets` are what select_docs_resident takes.
+        mask: a uint8 or bool tensor [len(ids)] on the device of `ids` -- the marks of duplicate_spans_resident and of
+        repetition_resident and the starts of ngram_overlap_resident as they are.  A position inside a document is kept
+        iff mask & bits is not 0 (drop=True: iff it is 0); ids in front of the first and behind the last document are
+        dropped.
+
+        Returns (ids', doc_offsets'): the kept ids in order, in the dtype of `ids`, and the int64 [n_docs + 1] offsets of
+        the same documents in ids' -- one that loses everything stays as an empty document, and document numbers do not
+        change --, both on the GPU.  out: as in select_docs_resident; it must not overlap `ids`.  Offsets that descend
+        or pass len(ids) raise ValueError.  Nothing but counters crosses PCIe."""
+        import torch
+        bits, flags = self._keep_values(bits, drop)
+        _check_ids(ids, (torch.int32, torch.int64), cuda=False)
+        dev = ids.device
+        doc_offsets = _check_doc_offsets(doc_offsets, dev, strict=True)
+        self._check_out(out, ids)
+        if not isinstance(mask, torch.Tensor) or mask.device != dev or mask.dtype not in (torch.uint8, torch.bool) \
+                or mask.dim() != 1 or not mask.is_contiguous():
+            raise TypeError("mask must be a 1-D contiguous uint8 or bool torch tensor on the device of ids")
+        if mask.numel() != ids.numel():
+            raise ValueError(f"the mask holds {mask.numel()} entries, there are {ids.numel()} ids")
+        _check_ids(ids, (torch.int32, torch.int64))
+        if mask.dtype == torch.bool:
+            mask, bits = mask.view(torch.uint8), 1  # (a bool is one byte, 0 or 1: its one bit is the mark)
+        doff = _place_doc_offsets(doc_offsets, dev)
+        n_docs = doff.numel() - 1
+        ooff = torch.empty(n_docs + 1, dtype=torch.int64, device=dev)
+        eng = engine(dev.index)
+        torch.cuda.current_stream(dev).synchronize()  # the caller's pending writes to ids and mask are done
+        res = self._resident_fill(
+            ids, out, ids.dtype, None, "ids", "keeps",
+            lambda dst, cap, *_: eng.keep_ids_resident(ids.data_ptr(), ids.element_size(), ids.numel(), doff.data_ptr(),
+                                                       n_docs, mask.data_ptr(), bits, flags, dst, cap, ooff.data_ptr()))
+        return res, ooff
+
+    def keep_ids(self, ids, doc_offsets, mask, *, device=None, **kw):
+        """keep_ids_resident() for ids and a mask on the host (the mask: anything np.asarray makes a flat uint8 or bool
+        array of): NumPy (ids', doc_offsets'), the ids int32 if an int32 array came in and int64 otherwise."""
+        import torch
+        self._keep_values(kw.get("bits", 0xFF), kw.get("drop", False))
+        if kw.get("out") is not None:
+            raise TypeError("keep_ids makes its own output")
+        arr, doc_offsets = self._host_stream(ids, doc_offsets)
+        m = np.asarray(mask)
+        if m.dtype not in (np.uint8, np.bool_) or m.ndim != 1:
+            raise TypeError("mask must be a flat uint8 or bool array")
+        if m.size != arr.size:
+            raise ValueError(f"the mask holds {m.size} entries, there are {arr.size} ids")
+        dev = _cuda_device(device)
+        res, ooff = self.keep_ids_resident(torch.from_numpy(arr).to(dev), doc_offsets,
+                                           torch.from_numpy(np.ascontiguousarray(m)).to(dev), **kw)
+        return res.cpu().numpy(), ooff.cpu().numpy()
+
+    def drop_duplicate_spans_resident(self, ids, doc_offsets, *, ngram=50, scope="earlier_doc", out=None):
+        """The stream without the stretches an earlier document already holds: duplicate_spans_resident() over whole
+        documents and keep_ids_resident(marks, bits=2, drop=True) in one call -- every position inside a seen window
+        goes, the first occurrence of every window stays.  Returns (ids', doc_offsets', stats): the id stream and the
+        offsets of the same documents in it as keep_ids_resident returns them, and the SpanDupStats with its marks;
+        stats.covered says what each document lost.  out: as in select_docs_resident."""
+        import torch
+        self._ngram_value(ngram)
+        self._scope_value(scope)
+        _check_ids(ids, (torch.int32, torch.int64), cuda=False)
+        self._check_out(out, ids)
+        stats, doff = self._duplicate_spans(ids, doc_offsets, ngram, scope, None, "head", True)
+        res, ooff = self.keep_ids_resident(ids, doff, stats.marks, bits=2, drop=True, out=out)
+        return res, ooff, stats
 
     # -- fixed-length rows from ids that live in HBM (DESIGN 4.4) ---------------------
     def rows_resident(self, ids, doc_offsets, row_len, *, stride=None, sep=None, pad=0, mode="pack", truncate="right",
