@@ -103,7 +103,10 @@ int bpe_set_stream(bpe_ctx *ctx, void *hip_stream);
  *   bpe_dup_spans_resident's passes: "ds_tile" (4096: stream positions per workgroup tile, a power of two from 64 to
  *   65536; a tile goes through LDS 2048 positions at a time, a smaller tile whole), "ds_hash_bits" (64, 0..64: only so
  *   many bits of a window's hash choose its first table slot and its tag; 0 puts every window of the stream onto one
- *   probe chain with tag 0 and makes every probe a full comparison -- the results are the same at every value). */
+ *   probe chain with tag 0 and makes every probe a full comparison -- the results are the same at every value);
+ *   bpe_segment_docs_resident's and bpe_segment_marks_resident's passes: "seg_tile" (4096: positions per workgroup
+ *   tile, a multiple of 64 from 64 to 65536), "seg_stage" (1024, 0..4096: ranges a tile of the marks pass stages in LDS;
+ *   0 makes every lane search global memory -- the results are the same at every value). */
 int bpe_set_option(bpe_ctx *ctx, const char *name, int64_t value);
 
 /* ---- input ----------------------------------------------------------------- */
@@ -828,6 +831,93 @@ int bpe_keep_ids_resident(bpe_ctx *ctx, const void *d_ids, int32_t id_width, uin
                           const uint8_t *d_mask, uint32_t bits, uint32_t flags,
                           void *d_out, uint64_t out_cap, uint64_t *d_out_offsets,
                           uint64_t *n_out, uint64_t *bad_doc);
+
+/* The segments of every document -- its lines, with the class table of Tokenizer.segment_classes -- as an id stream of
+ * its own, made on the device, so that every per-document call above becomes a per-segment call: the segment stream
+ * and its seg_offsets are an (ids, doc_offsets) pair (tests/segments_model.py: segment_docs).
+ *   class(t)         d_class[t] & 3 if 0 <= t < n_class, the id taken at its full width; 0 otherwise -- a negative id,
+ *                    an id beyond the table, an int64 id whose low 32 bits happen to index it.  n_class == 0 or
+ *                    d_class == NULL: every class is 0.  BPE_SEG_BREAK: a segment boundary lies BEHIND this id;
+ *                    BPE_SEG_SKIP: the id belongs to no segment
+ *   positions        only those of [off[0], off[n_docs]) take part
+ *   the walk         inside a document, position by position, with one bit of state, FRESH or OPEN, FRESH at the
+ *                    document's start.  A position without SKIP is content.  A content position seen in state FRESH
+ *                    starts a segment.  Content sets the state to OPEN; BREAK sets it to FRESH behind the position;
+ *                    SKIP alone leaves it as it is
+ *   segment          the content from one start up to the next boundary or the document's end: none is empty, a
+ *                    document may have none, none spans two documents
+ *   out              the content ids of all segments in order, in the width of d_ids.  With BPE_SEG_TAG_DOC every
+ *                    segment is preceded by one id that holds its document's number: equal segments of different
+ *                    documents then differ, and a per-document call compares the segments of one document only
+ *   seg_offsets[s]   where segment s begins in out (with BPE_SEG_TAG_DOC: its tag); seg_offsets[n_seg] = n_out
+ *   seg_doc[s]       the segment's document;  doc_seg_offsets[d]: the segments in documents below d, d = 0 .. n_docs
+ *   src_start[s], src_end[s]  a range of positions in d_ids: it begins at off[d] for the first segment of document d and
+ *                    at the segment's first content position otherwise; it ends at the first content position of the
+ *                    next segment of the same document, at off[d + 1] without one.  The ranges of a document's segments
+ *                    tile the document: skipped ids and separators trail the segment in front of them, leading ones go
+ *                    with the first segment
+ * Exact, and the result does not depend on scheduling: every output is a function of the inputs through scans.
+ *   d_ids, id_width  n ids of 4 (int32) or 8 (int64) bytes, read in place, never written
+ *   d_doc_offsets    validated on the device exactly as in bpe_rows_resident: ascending, none beyond n.  The first bad
+ *                    entry goes to *bad_doc (~0 if none), the call fails with BPE_E_ARG and nothing is written
+ *   d_class, n_class uint8 [n_class], only the two low bits of an entry are read
+ *   d_out, out_cap   d_out = NULL or out_cap = 0: a count-only call -- *n_out, *n_seg and d_doc_seg_offsets are written
+ *                    all the same, nothing else
+ *   d_seg_offsets, seg_cap  seg_cap + 1 words (NULL only in a count-only call);  d_seg_doc, d_src_start, d_src_end:
+ *                    int64 [seg_cap] each, each may be NULL;  d_doc_seg_offsets: n_docs + 1 words, may be NULL
+ *   *n_out, *n_seg   the totals (each may be NULL), set from the moment they are known
+ * out_cap < n_out or seg_cap < n_seg fails with BPE_E_CAP, both totals set: nothing is written to d_out or to any
+ * per-segment array, and never is anything written at or beyond a capacity.  n == 0, n_docs == 0 or empty documents
+ * only: BPE_OK with totals 0 (d_doc_seg_offsets zeroed, seg_offsets[0] = 0 unless count-only).
+ * BPE_E_ARG before any device work: id_width not 4 or 8, an unknown flag, d_ids = NULL with n > 0, d_doc_offsets NULL,
+ * d_seg_offsets NULL with an output, a misaligned pointer (d_ids and d_out to id_width, the others but d_class to 8
+ * bytes), d_out [out_cap] overlapping d_ids [n].  BPE_E_LIMIT, before anything is launched or allocated: n >= 2^32,
+ * n_docs >= 2^32 - 1, BPE_SEG_TAG_DOC with id_width == 4 and n_docs > 2^31 (a tag would not fit), n_class > 2^26.
+ * Passes (bpe_set_option: "seg_tile"): a segment start is no neighbour predicate -- SKIP ids in any number may lie
+ * between a boundary and the next content -- but a scan over the monoid {identity, ->FRESH, ->OPEN}, "the last event
+ * that is not the identity", a document start being ->FRESH in front of its position.  Document starts are a flag byte
+ * per position, written by a pass over the documents (empty documents and several at one position are harmless).
+ * CLASSIFY -- a tile per workgroup: the class of every id next to that flag, and the tile's summary byte; CARRY -- a
+ * launch of its own, one workgroup: the exclusive scan of the summaries, across any number of all-identity tiles;
+ * MARK -- per wave two ballots and a count of leading zeros below the lane, across the waves of a tile LDS, across
+ * tiles the carried byte: a start flag and an output length per position; two scans (k_scan_*); PLACE -- out,
+ * seg_offsets, seg_doc, src_start and the ends that a next segment sets (the one search of the call: per segment, for
+ * its document); ENDS -- the ends that a document's end sets.  No workgroup waits for another inside a launch, and
+ * every loop carries its bound.  Nothing is read outside [off[0], off[n_docs]).
+ * Runs on the ctx's stream and synchronises it before returning; keeps no pointer of the caller's; only the counters
+ * {first bad entry, off[0], off[n_docs]}, {n_out, n_seg} cross PCIe.
+ * Scratch: the output lengths, their scan and the start flags use the decode scratch (16 bytes per id), so the call drops
+ * a pending bpe_decode_batch result, as bpe_keep_ids_resident and bpe_select_docs_resident do; the flag bytes, the scan
+ * of the starts and the tile summaries (9 bytes per id) are a group of its own, grow-only, freed with the ctx.  Every
+ * other entry point's scratch and results are left alone. */
+#define BPE_SEG_BREAK 1u
+#define BPE_SEG_SKIP 2u
+#define BPE_SEG_TAG_DOC 1u
+int bpe_segment_docs_resident(bpe_ctx *ctx, const void *d_ids, int32_t id_width, uint64_t n,
+                              const uint64_t *d_doc_offsets, uint64_t n_docs,
+                              const uint8_t *d_class, uint64_t n_class, uint32_t flags,
+                              void *d_out, uint64_t out_cap, uint64_t *d_seg_offsets, uint64_t seg_cap,
+                              int64_t *d_seg_doc, int64_t *d_src_start, int64_t *d_src_end,
+                              uint64_t *d_doc_seg_offsets,
+                              uint64_t *n_out, uint64_t *n_seg, uint64_t *bad_doc);
+
+/* Per-segment verdicts back as the marks bpe_keep_ids_resident takes (tests/segments_model.py: segment_marks).
+ *   marks[p]         d_seg_val[s] where src_start[s] <= p < src_end[s], 0 at every other of the n positions: all n
+ *                    bytes are written
+ *   d_src_start, d_src_end  int64 [n_seg] each, as bpe_segment_docs_resident leaves them.  They must ascend without
+ *                    overlap inside [0, n]: entry s is bad if start[s] < 0, end[s] < start[s], end[s] > n, or
+ *                    start[s] < end[s - 1].  The first bad entry goes to *bad_seg (~0 if none), the call fails with
+ *                    BPE_E_ARG and nothing is written.  Empty ranges and gaps between ranges are fine
+ *   d_seg_val        uint8 [n_seg];  d_marks: uint8 [n]
+ * n_seg == 0 writes n zeros.  BPE_E_ARG before any device work: a NULL pointer that is needed (the three inputs with
+ * n_seg > 0, d_marks with n > 0), d_src_start or d_src_end not 8-byte aligned.  BPE_E_LIMIT: n >= 2^32, n_seg >= 2^32.
+ * Passes (bpe_set_option: "seg_tile", "seg_stage"): a check of the ranges; then, laid out by the positions, a tile per
+ * workgroup: one binary search for the tile's first range, the next "seg_stage" ranges staged in LDS, a lane searches
+ * there once and walks on; a tile in which more ranges begin than are staged searches global memory -- the pattern of
+ * bpe_select_docs_resident's placement.  Every loop carries its bound.  No scratch but a counter word.  Runs on the
+ * ctx's stream and synchronises it; only the counter {first bad range} crosses PCIe. */
+int bpe_segment_marks_resident(bpe_ctx *ctx, const int64_t *d_src_start, const int64_t *d_src_end, uint64_t n_seg,
+                               const uint8_t *d_seg_val, uint64_t n, uint8_t *d_marks, uint64_t *bad_seg);
 
 /* ---- measurement ------------------------------------------------------------ */
 #define BPE_PROF_WIDEN 0

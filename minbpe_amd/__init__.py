@@ -9,13 +9,13 @@ the first access to anything below raises ImportError.
 _EXPORTS = ("Tokenizer", "BasicTokenizer", "RegexTokenizer", "GPT4Tokenizer", "get_stats", "merge",
             "GPT2_SPLIT_PATTERN", "GPT4_SPLIT_PATTERN", "render_token", "replace_control_characters",
             "Engine", "synth_text", "split_offsets", "version", "NgramIndex", "RepetitionStats",
-            "SpanDupStats")
+            "SpanDupStats", "Segments", "LineDupStats")
 
 try:
     from .tokenizer import (  # noqa: F401
         Tokenizer, BasicTokenizer, RegexTokenizer, GPT4Tokenizer, get_stats, merge,
         GPT2_SPLIT_PATTERN, GPT4_SPLIT_PATTERN, render_token, replace_control_characters, NgramIndex,
-        RepetitionStats, SpanDupStats,
+        RepetitionStats, SpanDupStats, Segments, LineDupStats,
     )
     from ._native import Engine, synth_text, split_offsets, version  # noqa: F401
     _load_error = None

@@ -124,6 +124,9 @@ _SIGS = {
                                          _p, _p, _p, C.POINTER(_u64), C.POINTER(_u64), C.POINTER(_u64), C.POINTER(_u64)]),
     "bpe_keep_ids_resident": (C.c_int, [_p, _p, _i32, _u64, _p, _u64, _p, C.c_uint32, C.c_uint32, _p, _u64, _p,
                                         C.POINTER(_u64), C.POINTER(_u64)]),
+    "bpe_segment_docs_resident": (C.c_int, [_p, _p, _i32, _u64, _p, _u64, _p, _u64, C.c_uint32, _p, _u64, _p, _u64,
+                                            _p, _p, _p, _p, C.POINTER(_u64), C.POINTER(_u64), C.POINTER(_u64)]),
+    "bpe_segment_marks_resident": (C.c_int, [_p, _p, _p, _u64, _p, _u64, _p, C.POINTER(_u64)]),
     "bpe_prof_reset": (C.c_int, [_p]),
     "bpe_prof_read": (C.c_int, [_p, _p, _p, _p]),
     "bpe_encode_uses_16bit": (C.c_int, [_p, C.c_int32]),
@@ -322,6 +325,26 @@ ROWS_HAS_SEP, ROWS_TRUNC_LEFT, ROWS_PAD_LEFT = 1, 2, 4
 SELECT_TAIL = 1
 SPANS_ANYWHERE = 2
 KEEP_DROP = 1
+SEG_BREAK, SEG_SKIP = 1, 2
+SEG_TAG_DOC = 1
+
+
+class BadSegment(IndexError):
+    """bpe_segment_marks_resident met a range that descends, overlaps the one before or leaves [0, n]; index = the
+    lowest such range."""
+
+    def __init__(self, index, msg):
+        super().__init__(msg)
+        self.index = index
+
+
+class SegmentsTooSmall(OutputTooSmall):
+    """bpe_segment_docs_resident was given too little room; needed, needed_segments = the ids and the segments of the
+    stream."""
+
+    def __init__(self, needed, needed_segments, msg):
+        super().__init__(needed, msg)
+        self.needed_segments = needed_segments
 
 
 def _ptr(a):
@@ -891,6 +914,41 @@ class Engine:
             raise OutputTooSmall(int(no.value), (_lib.bpe_last_error(self._h) or b"").decode())
         self._check(rc)
         return int(no.value)
+
+    # -- segments of documents ---------------------------------------------------------
+    def segment_docs_resident(self, d_ids: int, id_width: int, n: int, d_doc_off: int, n_docs: int, d_class: int = 0,
+                              n_class: int = 0, flags: int = 0, d_out: int = 0, out_cap: int = 0, d_seg_off: int = 0,
+                              seg_cap: int = 0, d_seg_doc: int = 0, d_src_start: int = 0, d_src_end: int = 0,
+                              d_doc_seg_off: int = 0):
+        """bpe_segment_docs_resident: d_ids (n ids of id_width = 4 or 8 bytes), d_doc_off (n_docs + 1 uint64), d_class
+        (n_class uint8: SEG_BREAK | SEG_SKIP per id), d_out (room for out_cap ids of the same width; 0 = only count),
+        d_seg_off (seg_cap + 1 uint64), the columns d_seg_doc, d_src_start, d_src_end (seg_cap int64 each, 0 = not
+        wanted) and d_doc_seg_off (n_docs + 1 uint64, 0 = not wanted) are device addresses.  flags SEG_TAG_DOC = every
+        segment is preceded by an id holding its document's number.  Returns (ids of the segment stream, segments).
+        Offsets that descend or pass n raise BadDocOffsets(entry); too little room raises SegmentsTooSmall."""
+        no, ns, bad_doc = _u64(0), _u64(0), _u64(0)
+        rc = _lib.bpe_segment_docs_resident(self._h, C.c_void_p(d_ids), id_width, n, C.c_void_p(d_doc_off), n_docs,
+                                            C.c_void_p(d_class), n_class, flags, C.c_void_p(d_out), out_cap,
+                                            C.c_void_p(d_seg_off), seg_cap, C.c_void_p(d_seg_doc), C.c_void_p(d_src_start),
+                                            C.c_void_p(d_src_end), C.c_void_p(d_doc_seg_off), C.byref(no), C.byref(ns),
+                                            C.byref(bad_doc))
+        if rc == BPE_E_ARG and bad_doc.value != 0xFFFFFFFFFFFFFFFF:
+            raise BadDocOffsets(int(bad_doc.value), (_lib.bpe_last_error(self._h) or b"").decode())
+        if rc == BPE_E_CAP:
+            raise SegmentsTooSmall(int(no.value), int(ns.value), (_lib.bpe_last_error(self._h) or b"").decode())
+        self._check(rc)
+        return int(no.value), int(ns.value)
+
+    def segment_marks_resident(self, d_src_start: int, d_src_end: int, n_seg: int, d_seg_val: int, n: int, d_marks: int):
+        """bpe_segment_marks_resident: d_src_start, d_src_end (n_seg int64 each), d_seg_val (n_seg uint8) and d_marks (n
+        uint8, all written) are device addresses: marks[p] = val[s] inside range s, 0 elsewhere.  Ranges that descend,
+        overlap or leave [0, n] raise BadSegment(entry); nothing is written then."""
+        bad = _u64(0)
+        rc = _lib.bpe_segment_marks_resident(self._h, C.c_void_p(d_src_start), C.c_void_p(d_src_end), n_seg,
+                                             C.c_void_p(d_seg_val), n, C.c_void_p(d_marks), C.byref(bad))
+        if rc == BPE_E_ARG and bad.value != 0xFFFFFFFFFFFFFFFF:
+            raise BadSegment(int(bad.value), (_lib.bpe_last_error(self._h) or b"").decode())
+        self._check(rc)
 
     # -- measurement ----------------------------------------------------------------
     def prof_reset(self):

@@ -46,6 +46,10 @@ union ScratchWords {
               // not find}, and the documents with a seen window (the last four read back as one block)
         unsigned long long bad, ends[2], counts[3], seen_docs;
     } ds;
+    struct {  // bpe_segment_docs_resident: `rows` for its offsets check, and {n_out, n_seg}; bpe_segment_marks_resident:
+              // the first bad range
+        unsigned long long bad, ends[2], totals[2];
+    } seg;
     struct {  // encode_batch_impl (min_rank and starts: the stream-wide rounds of its longest chunks)
         unsigned long long nlong, total;
         uint32_t min_rank, pad;
@@ -411,6 +415,14 @@ struct bpe_ctx {
     int ds_tile = 4096;       // option "ds_tile": stream positions per workgroup tile of the window and cover passes, a power of two
                               // 
     int ds_hash_bits = 64;    // option "ds_hash_bits": bits of the window hash that choose the first slot and the tag (tests: 0 = none)
+    // bpe_segment_docs_resident (k_segment.hip): a scratch of its own (grow-only), by the positions: a flag byte each
+    // (document start | class << 1), the scan of the segment starts with its block sums, and a summary byte per tile of 64
+    // positions or more.  The output lengths, their scan and the start flags live in the decode scratch
+    DevPtr<uint8_t> d_seg_flag, d_seg_sum;
+    DevPtr<unsigned long long> d_seg_off, d_seg_bsum;
+    uint64_t cap_seg_n = 0;
+    int seg_tile = 4096;      // option "seg_tile": positions per workgroup tile of the segment passes and the marks pass, a multiple of 64
+    int seg_stage = 1024;     // option "seg_stage": ranges a tile of the marks pass stages in LDS (0: every lane searches global memory, the cross-check form)
     // bpe_token_spans_resident (k_spans.hip): leads | cont << 31 of every table entry, made on the device by the first
     // call after a bpe_decode_set_vocab; the second scan channel and the documents' bases (grow-only)
     DevPtr<uint32_t> d_dec_meta;

@@ -102,7 +102,8 @@ const OptRow OPTIONS[] = {
 // (bpe_select_docs_resident): elements, output starts; document de-duplication (bpe_dup_docs_resident): positions, ids, bits;
 // MinHash signatures (bpe_minhash_resident): positions; n-gram overlap (bpe_ngram_index_resident,
 // bpe_ngram_overlap_resident): positions, bits; repetition statistics (bpe_repeat_stats_resident): positions, bits; span
-// de-duplication (bpe_dup_spans_resident): positions, bits
+// de-duplication (bpe_dup_spans_resident): positions, bits; segments (bpe_segment_docs_resident,
+// bpe_segment_marks_resident): positions, ranges
 const OptRow OPTIONS_MORE[] = {
     OPT_STEP(count_lds_bins, 256, COUNT_LDS_BINS_MAX, 256),
     OPT(count_flush, 64, 1ll << 31),
@@ -119,6 +120,8 @@ const OptRow OPTIONS_MORE[] = {
     OPT(rp_hash_bits, 0, 64),
     OPT_NAMED("ds_tile", ds_tile, OPT_POW2, 64, DS_TILE_MAX, 1),
     OPT(ds_hash_bits, 0, 64),
+    OPT_STEP(seg_tile, 64, SEG_TILE_MAX, 64),
+    OPT(seg_stage, 0, SEG_STAGE_MAX),
 };
 
 #undef OPT_RAW

@@ -61,6 +61,7 @@ struct ProfEv {
 #include "api/api_repeat.hip"
 #include "api/api_dupspans.hip"
 #include "api/api_keep.hip"
+#include "api/api_segment.hip"
 #include "api/api_dp.hip"
 #include "api/api_rccl.hip"
 #include "api/api_prof.hip"

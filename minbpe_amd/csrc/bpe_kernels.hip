@@ -73,4 +73,5 @@
 #include "kernels/k_repeat.hip"
 #include "kernels/k_dupspans.hip"
 #include "kernels/k_keep.hip"
+#include "kernels/k_segment.hip"
 #include "kernels/k_util.hip"

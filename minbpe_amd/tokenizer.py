@@ -195,6 +195,25 @@ class SpanDupStats(collections.namedtuple("SpanDupStats", "length windows seen c
     __slots__ = ()
 
 
+class Segments(collections.namedtuple("Segments", "ids seg_offsets seg_doc doc_seg_offsets src_start src_end")):
+    """What Tokenizer.segments_resident returns: ids, the content ids of all segments (lines) in order -- with
+    tag_docs=True each preceded by one id that holds its document's number --, and seg_offsets [n_seg + 1], where each
+    begins in them: together an (ids, doc_offsets) pair that every per-document method takes.  seg_doc [n_seg]: the
+    segment's document; doc_seg_offsets [n_docs + 1]: the segments in the documents below; src_start, src_end [n_seg]:
+    the segment's range of positions in the stream it came from -- the ranges of a document's segments tile it."""
+    __slots__ = ()
+
+
+class LineDupStats(collections.namedtuple("LineDupStats", "length lines dup_lines content dup_content marks")):
+    """What Tokenizer.duplicate_lines_resident returns: per document its length, its lines, those of them that are
+    duplicates, its content ids (the ids that belong to a line) and those of them inside a duplicate line; marks: a byte
+    per id (bit 0: the id lies in the source range of a duplicate line), or None."""
+    __slots__ = ()
+
+
+_LINE_SPACE = b" \t\n\r\x0b\x0c"  # the six ASCII whitespace bytes (what bytes.isspace() knows)
+
+
 class Tokenizer:
     """Base class: state, vocab construction, save/load (base.py:66-165)."""
 
@@ -776,6 +795,12 @@ class Tokenizer:
         int64 [n_docs]: the number of copies at every d with first[d] == d and 0 elsewhere.  n_distinct_docs then holds
         the number of distinct documents.  Offsets that descend or pass len(ids) raise ValueError.  Nothing but counters
         crosses PCIe."""
+        first, counts, self._n_distinct_docs = self._duplicate_docs(ids, doc_offsets, max_len, keep, return_counts)
+        return (first, counts) if return_counts else first
+
+    def _duplicate_docs(self, ids, doc_offsets, max_len=None, keep="head", return_counts=False):
+        """duplicate_docs_resident() without its counter: (first, counts or None, the number of distinct documents) --
+        for the methods that run it on a stream of their own making and owe the caller no n_distinct_docs"""
         import torch
         max_len, flags = self._select_values(max_len, keep)
         _check_ids(ids, (torch.int32, torch.int64), cuda=False)
@@ -788,10 +813,9 @@ class Tokenizer:
         counts = torch.empty(n_docs, dtype=torch.int64, device=dev) if return_counts else None
         eng = engine(dev.index)
         torch.cuda.current_stream(dev).synchronize()  # the caller's pending writes to ids (and the upload above) are done
-        self._n_distinct_docs = eng.dup_docs_resident(ids.data_ptr(), ids.element_size(), ids.numel(), doff.data_ptr(),
-                                                      n_docs, max_len, flags, first.data_ptr(),
-                                                      counts.data_ptr() if return_counts else 0)
-        return (first, counts) if return_counts else first
+        n_distinct = eng.dup_docs_resident(ids.data_ptr(), ids.element_size(), ids.numel(), doff.data_ptr(), n_docs, max_len,
+                                           flags, first.data_ptr(), counts.data_ptr() if return_counts else 0)
+        return first, counts, n_distinct
 
     def unique_docs_resident(self, ids, doc_offsets, *, max_len=None, keep="head", out=None):
         """One copy of every document, the first, in the order of the stream: duplicate_docs_resident() and
@@ -1454,6 +1478,305 @@ class Tokenizer:
         stats, doff = self._duplicate_spans(ids, doc_offsets, ngram, scope, None, "head", True)
         res, ooff = self.keep_ids_resident(ids, doff, stats.marks, bits=2, drop=True, out=out)
         return res, ooff, stats
+
+    # -- the lines of every document as a stream of their own -------------
+    @property
+    def n_segments(self):
+        """The number of segments the last segments_resident() of this tokenizer found (and the methods built on it,
+        and their host forms); None before the first."""
+        return getattr(self, "_n_segments", None)
+
+    @property
+    def n_segment_ids(self):
+        """The ids of that call's segment stream, tags included; None before the first."""
+        return getattr(self, "_n_segment_ids", None)
+
+    @property
+    def n_duplicate_lines(self):
+        """The number of duplicate lines the last duplicate_lines_resident() of this tokenizer found (and the methods
+        built on it, and their host forms); None before the first."""
+        return getattr(self, "_n_duplicate_lines", None)
+
+    @property
+    def n_docs_with_duplicate_lines(self):
+        """The documents with a duplicate line in that call; None before the first."""
+        return getattr(self, "_n_docs_with_duplicate_lines", None)
+
+    @staticmethod
+    def _segment_unit(unit):
+        """ValueError for a unit that is not offered"""
+        if not isinstance(unit, str) or unit != "line":
+            raise ValueError(f"unit={unit!r} not understood: 'line'")
+
+    def segment_classes(self, unit="line"):
+        """The class of every one of the 256 + M dense ids for splitting documents into lines, a uint8 array computed
+        from the vocabulary: SEG_SKIP (2) for a token whose bytes are all ASCII whitespace (space, \\t, \\n, \\r, \\x0b,
+        \\x0c) -- it belongs to no line --, SEG_BREAK (1) for a token that contains \\n -- a line ends behind it.  A
+        newline token itself has both.  Special tokens and ids outside the table have class 0: content that ends no
+        line.  The rule is token-granular: a newline in the MIDDLE of a token ends the line behind the whole token, so
+        the whole token belongs to the line it ends.  The GPT-2 and GPT-4 split patterns never let a merge put a
+        letter behind a newline, so this can only happen with BasicTokenizer.  Only unit="line" is offered."""
+        self._segment_unit(unit)
+        cached = getattr(self, "_segment_classes", None)
+        if cached is not None and cached[0] is self.vocab and cached[1] == len(self.merges):
+            return cached[2].copy()
+        n = 256 + len(self.merges)
+        cls = np.zeros(n, dtype=np.uint8)
+        for idx in range(n):
+            tok = self.vocab[idx]
+            if tok and not tok.strip(_LINE_SPACE):
+                cls[idx] |= _native.SEG_SKIP
+            if b"\n" in tok:
+                cls[idx] |= _native.SEG_BREAK
+        self._segment_classes = (self.vocab, len(self.merges), cls)
+        return cls.copy()
+
+    def _segment_classes_arg(self, unit, classes):
+        """the class table a call splits by, checked: the caller's (a flat uint8 array or tensor), else this
+        vocabulary's for `unit`"""
+        import torch
+        self._segment_unit(unit)
+        if classes is None:
+            return self.segment_classes(unit)
+        if isinstance(classes, torch.Tensor):
+            if classes.dtype != torch.uint8 or classes.dim() != 1 or not classes.is_contiguous():
+                raise TypeError("classes must be a flat contiguous uint8 array or tensor")
+            return classes
+        arr = np.asarray(classes)
+        if arr.dtype != np.uint8 or arr.ndim != 1:
+            raise TypeError("classes must be a flat contiguous uint8 array or tensor")
+        return np.ascontiguousarray(arr)
+
+    @staticmethod
+    def _tag_value(tag_docs):
+        """the library's flag; ValueError for a value that is no truth value"""
+        if not isinstance(tag_docs, (bool, np.bool_)):
+            raise ValueError("tag_docs must be True or False")
+        return _native.SEG_TAG_DOC if tag_docs else 0
+
+    def segments_resident(self, ids, doc_offsets, *, unit="line", classes=None, tag_docs=False, out=None):
+        """The lines of every document as an id stream of their own, made on the device; not in the reference.  `ids`
+        and `doc_offsets` are what select_docs_resident takes.  A document is walked id by id: an id without SEG_SKIP
+        is content, the first content after a boundary starts a segment, an id with SEG_BREAK puts a boundary behind
+        itself, and a document's end is one -- so no segment is empty, a document may have none, and whitespace in any
+        amount between two lines belongs to neither.  classes: a uint8 array or tensor of the caller's own, one class
+        per id (ids outside it have class 0), to split at a special token or at sentence ends instead; it overrides unit.
+
+        Returns a Segments of tensors on the device of `ids`; (segments.ids, segments.seg_offsets) is an (ids,
+        doc_offsets) pair: duplicate_docs_resident on it is exact line de-duplication, minhash_resident near-duplicate
+        lines, ngram_overlap_resident contamination per line.  tag_docs=True puts the document's number in front of
+        every segment as one id, so that those calls compare the lines of one document only.  out: as in
+        select_docs_resident.  n_segments and n_segment_ids then hold the counters.  Offsets that descend or pass
+        len(ids) raise ValueError.  Nothing but counters crosses PCIe (and, once per vocabulary and device, the classes)."""
+        return self._segments(ids, doc_offsets, unit, classes, tag_docs, out)[0]
+
+    def _segments(self, ids, doc_offsets, unit, classes, tag_docs, out):
+        """(Segments, the offsets on the device)"""
+        import torch
+        cls = self._segment_classes_arg(unit, classes)
+        flags = self._tag_value(tag_docs)
+        _check_ids(ids, (torch.int32, torch.int64), cuda=False)
+        dev = ids.device
+        doc_offsets = _check_doc_offsets(doc_offsets, dev, strict=True)
+        self._check_out(out, ids)
+        if isinstance(cls, torch.Tensor) and cls.device != dev:
+            raise TypeError("classes must be on the device of ids")
+        _check_ids(ids, (torch.int32, torch.int64))
+        doff = _place_doc_offsets(doc_offsets, dev)
+        n_docs = doff.numel() - 1
+        if isinstance(cls, torch.Tensor):
+            d_cls = cls
+        else:  # (this vocabulary's table stays on the device it was last used on)
+            held = getattr(self, "_segment_classes_dev", None)
+            if classes is None and held is not None and held[0] is self._segment_classes[2] and held[1] == dev:
+                d_cls = held[2]
+            else:
+                d_cls = torch.from_numpy(cls).to(dev)
+                if classes is None:
+                    self._segment_classes_dev = (self._segment_classes[2], dev, d_cls)
+        dso = torch.empty(n_docs + 1, dtype=torch.int64, device=dev)
+        eng = engine(dev.index)
+        torch.cuda.current_stream(dev).synchronize()  # the caller's pending writes to ids (and the uploads above) are done
+        cols, totals = [], [0, 0]
+
+        def run(dst, cap):
+            room = (0, 0, 0, 0, 0, 0, 0) if not cols else (dst, cap, cols[0].data_ptr(), cols[1].numel(),
+                                                           cols[1].data_ptr(), cols[2].data_ptr(), cols[3].data_ptr())
+            totals[:] = eng.segment_docs_resident(ids.data_ptr(), ids.element_size(), ids.numel(), doff.data_ptr(), n_docs,
+                                                  d_cls.data_ptr(), d_cls.numel(), flags, *room, dso.data_ptr())
+            return totals[0]
+
+        def native_call(dst, cap, *_):
+            if not cols:  # the count comes first: it sizes the per-segment columns
+                run(0, 0)
+                cols.append(torch.zeros(totals[1] + 1, dtype=torch.int64, device=dev))
+                cols.extend(torch.empty(totals[1], dtype=torch.int64, device=dev) for _ in range(3))
+                torch.cuda.current_stream(dev).synchronize()
+            return run(dst, cap) if dst and cap else totals[0]
+
+        res = self._resident_fill(ids, out, ids.dtype, None, "ids", "segments", native_call)
+        self._n_segment_ids, self._n_segments = totals
+        return Segments(res, cols[0], cols[1], dso, cols[2], cols[3]), doff
+
+    def segment_marks_resident(self, segments, values, n):
+        """A verdict per segment as a mark per id: marks[p] = values[s] for every position p of the source range of
+        segment s, 0 at every other of the n positions -- the mask keep_ids_resident takes.  segments: what
+        segments_resident returned for a stream of n ids; values: a uint8 or bool tensor [n_segments] on its device.
+        Returns a uint8 tensor [n]."""
+        import torch
+        if not isinstance(segments, Segments):
+            raise TypeError("segments must be what segments_resident returned")
+        if isinstance(n, bool) or not isinstance(n, (int, np.integer)) or n < 0:
+            raise ValueError("n must be the number of ids of the stream the segments came from")
+        start, end = segments.src_start, segments.src_end
+        for t in (start, end):
+            if not isinstance(t, torch.Tensor) or not t.is_cuda or t.dtype != torch.int64 or t.dim() != 1 \
+                    or not t.is_contiguous() or t.numel() != start.numel() or t.device != start.device:
+                raise TypeError("segments must hold the int64 tensors on the GPU that segments_resident returned")
+        if not isinstance(values, torch.Tensor) or values.device != start.device or values.dim() != 1 \
+                or values.dtype not in (torch.uint8, torch.bool) or not values.is_contiguous():
+            raise TypeError("values must be a 1-D contiguous uint8 or bool torch tensor on the device of the segments")
+        if values.numel() != start.numel():
+            raise ValueError(f"there are {values.numel()} values for {start.numel()} segments")
+        dev = start.device
+        if values.dtype == torch.bool:
+            values = values.view(torch.uint8)
+        marks = torch.empty(int(n), dtype=torch.uint8, device=dev)
+        eng = engine(dev.index)
+        torch.cuda.current_stream(dev).synchronize()  # the caller's pending writes to the values are done
+        try:
+            eng.segment_marks_resident(start.data_ptr(), end.data_ptr(), start.numel(), values.data_ptr(), int(n),
+                                       marks.data_ptr())
+        except _native.BadSegment as e:
+            raise ValueError(f"segment {e.index}: its source range does not fit a stream of {n} ids") from None
+        return marks
+
+    @staticmethod
+    def _line_scope(scope):
+        """tag_docs of a scope; ValueError for a scope that is not known"""
+        if not isinstance(scope, str) or scope not in ("in_doc", "stream"):
+            raise ValueError(f"scope={scope!r} not understood: 'in_doc' or 'stream'")
+        return scope == "in_doc"
+
+    @staticmethod
+    def _min_len_value(min_len):
+        if isinstance(min_len, bool) or not isinstance(min_len, (int, np.integer)) or min_len < 1:
+            raise ValueError("min_len must be an integer of 1 or more")
+        return int(min_len)
+
+    def duplicate_lines_resident(self, ids, doc_offsets, *, scope="in_doc", min_len=1, unit="line", classes=None,
+                                 return_marks=False):
+        """Which lines of every document are copies of an earlier line, found on the device: the line half of the
+        Gopher / MassiveText repetition rules (scope="in_doc": an equal line stands earlier in the SAME document) and
+        CCNet-style line de-duplication (scope="stream": an equal line stands anywhere earlier in the stream -- menus,
+        cookie banners, "read more"); not in the reference.  segments_resident() with tag_docs=(scope == "in_doc"), then
+        duplicate_docs_resident() on the segment stream: a line is a duplicate iff it is not the first of its copies and
+        has at least min_len content ids.  Lines are compared as their content ids, exactly, whitespace ids left out.
+        unit, classes: as in segments_resident.
+
+        Returns a LineDupStats of int64 tensors [n_docs] on the device of `ids`: length, lines, dup_lines, content (the
+        ids that belong to a line), dup_content (those of them in a duplicate line); marks is None, or with
+        return_marks=True a uint8 tensor [len(ids)] with bit 0 set over the whole source range of every duplicate line
+        -- the line, and the whitespace behind it -- which keep_ids_resident(bits=1, drop=True) cuts out.
+        n_duplicate_lines and n_docs_with_duplicate_lines then hold the counters."""
+        return self._duplicate_lines(ids, doc_offsets, scope, min_len, unit, classes, return_marks)[0]
+
+    def _duplicate_lines(self, ids, doc_offsets, scope, min_len, unit, classes, return_marks):
+        """(LineDupStats, the offsets on the device)"""
+        import torch
+        tag = self._line_scope(scope)
+        min_len = self._min_len_value(min_len)
+        seg, doff = self._segments(ids, doc_offsets, unit, classes, tag, None)
+        dev = ids.device
+        n_seg, n_docs = seg.seg_doc.numel(), doff.numel() - 1
+        content_len = seg.seg_offsets[1:] - seg.seg_offsets[:-1] - int(tag)
+        if n_seg:
+            first = self._duplicate_docs(seg.ids, seg.seg_offsets)[0]  # (n_distinct_docs speaks of the caller's documents)
+            dup = (first != torch.arange(n_seg, dtype=torch.int64, device=dev)) & (content_len >= min_len)
+        else:
+            dup = torch.zeros(0, dtype=torch.bool, device=dev)
+
+        def fold(values):
+            return torch.zeros(n_docs, dtype=torch.int64, device=dev).index_add_(0, seg.seg_doc, values)
+
+        stats = LineDupStats(doff[1:] - doff[:-1], seg.doc_seg_offsets[1:] - seg.doc_seg_offsets[:-1],
+                             fold(dup.to(torch.int64)), fold(content_len), fold(content_len * dup),
+                             self.segment_marks_resident(seg, dup, ids.numel()) if return_marks else None)
+        self._n_duplicate_lines = int(dup.sum().item())
+        self._n_docs_with_duplicate_lines = int((stats.dup_lines > 0).sum().item())
+        return stats, doff
+
+    @staticmethod
+    def _line_fractions(line_frac, content_frac):
+        for name, v in (("line_frac", line_frac), ("content_frac", content_frac)):
+            if isinstance(v, bool) or not isinstance(v, (int, float, np.integer, np.floating)) or not 0 <= v <= 1:
+                raise ValueError(f"{name} must be a number from 0 to 1")
+        return float(line_frac), float(content_frac)
+
+    def repetitive_line_docs_resident(self, ids, doc_offsets, *, line_frac=.30, content_frac=.20, min_len=1, unit="line",
+                                      classes=None):
+        """The line half of the Gopher / MassiveText repetition rules, on the device: flagged, a bool tensor [n_docs]:
+        document d is flagged iff dup_lines > line_frac * lines or dup_content > content_frac * content of
+        duplicate_lines_resident(scope="in_doc"), both sides compared in float64; a document without a line is never
+        flagged.  The defaults are Gopher's: more than 30 % of the lines, or 20 % of the content, are duplicate lines.
+        (repetitive_docs_resident is the n-gram half.)"""
+        line_frac, content_frac = self._line_fractions(line_frac, content_frac)
+        st = self._duplicate_lines(ids, doc_offsets, "in_doc", min_len, unit, classes, False)[0]
+        return (st.dup_lines.double() > line_frac * st.lines.double()) | \
+            (st.dup_content.double() > content_frac * st.content.double())
+
+    def drop_duplicate_lines_resident(self, ids, doc_offsets, *, scope="stream", min_len=1, unit="line", classes=None,
+                                      out=None):
+        """The stream without its duplicate lines: duplicate_lines_resident(return_marks=True) and
+        keep_ids_resident(marks, bits=1, drop=True) in one call -- every duplicate line goes with the whitespace behind
+        it, the first copy of every line stays.  Returns (ids', doc_offsets', stats) as drop_duplicate_spans_resident
+        does; stats.dup_lines says what each document lost.  out: as in select_docs_resident."""
+        import torch
+        self._line_scope(scope)
+        self._min_len_value(min_len)
+        self._segment_classes_arg(unit, classes)
+        _check_ids(ids, (torch.int32, torch.int64), cuda=False)
+        self._check_out(out, ids)
+        stats, doff = self._duplicate_lines(ids, doc_offsets, scope, min_len, unit, classes, True)
+        res, ooff = self.keep_ids_resident(ids, doff, stats.marks, bits=1, drop=True, out=out)
+        return res, ooff, stats
+
+    def _host_lines(self, ids, doc_offsets, device, kw):
+        """the arguments of the host forms, checked before a device is named -> (ids on the GPU, offsets)"""
+        import torch
+        if kw.get("out") is not None:
+            raise TypeError("the host forms make their own output")
+        self._segment_classes_arg(kw.get("unit", "line"), kw.get("classes"))
+        if "tag_docs" in kw:
+            self._tag_value(kw["tag_docs"])
+        if "scope" in kw:
+            self._line_scope(kw["scope"])
+        self._min_len_value(kw.get("min_len", 1))
+        arr, doc_offsets = self._host_stream(ids, doc_offsets)
+        dev = _cuda_device(device)
+        if isinstance(kw.get("classes"), torch.Tensor):
+            kw["classes"] = kw["classes"].to(dev)
+        return torch.from_numpy(arr).to(dev), doc_offsets
+
+    def segments(self, ids, doc_offsets, *, device=None, **kw):
+        """segments_resident() for ids on the host (a list or an array of integers; an int32 array goes up as int32,
+        anything else as int64): a Segments of NumPy arrays.  device: the GPU's index (default: the process-wide
+        engine's)."""
+        d_ids, doc_offsets = self._host_lines(ids, doc_offsets, device, kw)
+        return Segments(*[t.cpu().numpy() for t in self.segments_resident(d_ids, doc_offsets, **kw)])
+
+    def duplicate_lines(self, ids, doc_offsets, *, device=None, **kw):
+        """duplicate_lines_resident() for ids on the host: a LineDupStats of NumPy arrays."""
+        d_ids, doc_offsets = self._host_lines(ids, doc_offsets, device, kw)
+        res = self.duplicate_lines_resident(d_ids, doc_offsets, **kw)
+        return LineDupStats(*[None if t is None else t.cpu().numpy() for t in res])
+
+    def drop_duplicate_lines(self, ids, doc_offsets, *, device=None, **kw):
+        """drop_duplicate_lines_resident() for ids on the host: NumPy (ids', doc_offsets', stats), the ids int32 if an
+        int32 array came in and int64 otherwise."""
+        d_ids, doc_offsets = self._host_lines(ids, doc_offsets, device, kw)
+        res, ooff, stats = self.drop_duplicate_lines_resident(d_ids, doc_offsets, **kw)
+        return res.cpu().numpy(), ooff.cpu().numpy(), LineDupStats(*[None if t is None else t.cpu().numpy() for t in stats])
 
     # -- fixed-length rows from ids that live in HBM (DESIGN 4.4) ---------------------
     def rows_resident(self, ids, doc_offsets, row_len, *, stride=None, sep=None, pad=0, mode="pack", truncate="right",
